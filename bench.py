@@ -30,7 +30,21 @@ them).  A rank whose LOCAL_RANK has no GPU fails (RCCL), except in the
 one-GPU rehearsal TSG_BENCH_BACKEND=gloo, where ranks share the visible
 devices.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--strong] [--timeout S]
+A plain run does only what the headline needs: set-up, warm-up, the K timed
+steps, the outputs (--dump-outputs DIR) and the line.  Everything else the
+benchmark measures or checks runs behind --full: the second timing pass with
+an event pair around every launch (the kernel alone when a step is two
+launches), the end-to-end leg through host pointers, the CPU baselines, and at
+world > 1 the all-gather alone and the checks of the gathered blocks.  Without
+--full those keys of the line are null.
+
+--dump-outputs DIR writes what the timed path computed in its last step, the
+array a caller receives, as DIR/Y.npy (float32): Y itself when it is small, else
+a fixed seeded sample of its elements (DUMP_MAX_ELEMS).  The inputs depend
+only on the arguments, so two builds can be compared output for output.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
+                    [--strong] [--timeout S]
 """
 from __future__ import annotations
 
@@ -55,6 +69,8 @@ PROFILE_PMC = os.path.join(REPO, "profiles", "r06final_pmc_summary.json")
 # lane, 128 adds/clk/CU (measured 121 in scripts/issue_micro.hip), x 256 CUs x
 # 2.4 GHz = 78.6 T adds/s (the 157.3 TFLOP/s fp32 vector spec counts an FMA as 2).
 VALU_PEAK_TADDS = 128 * 256 * 2.4e9 / 1e12
+DUMP_MAX_ELEMS = 8 << 20  # --dump-outputs: at most 32 MiB of float32
+DUMP_SEED = 20240607
 
 
 def parse():
@@ -62,6 +78,11 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements and checks: per-launch event-pair timing, the end-to-end "
+                         "leg through host pointers, the CPU baselines, the all-gather alone and the block checks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's Y (or a fixed seeded sample of it) as DIR/Y.npy")
     ap.add_argument("--M", type=int, default=4096)
     ap.add_argument("--K", type=int, default=4096)
     ap.add_argument("--N", type=int, default=16384, help="columns per GPU (weak) or in total (--strong)")
@@ -73,11 +94,14 @@ def parse():
     ap.add_argument("--seed-w", type=int, default=42)
     ap.add_argument("--seed-x", type=int, default=12345)
     ap.add_argument("--cpu-rows", type=int, default=512,
-                    help="rows of the bounded single-thread CPU-baseline samples (0 = skip the CPU legs)")
+                    help="rows of the bounded single-thread CPU-baseline samples of --full (0 = skip the CPU legs)")
     ap.add_argument("--timeout", type=float, default=420.0,
                     help="launcher deadline in seconds (--gpus N > 1 without torchrun): ranks still running "
                          "then are stopped by PID and the launcher exits 124")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 def host_info() -> dict:
@@ -138,6 +162,20 @@ def cpu_baseline(X, csp, csn, rip, rin, K, N, s, Y_gpu, rows1):
                        f"BaseTCSC + OpenMP on {threads} threads (the box's CPU share; "
                        f"{host['cpus_in_affinity']} CPUs in affinity) over all {M} rows"),
             "host": host, "legs": legs}
+
+
+def dump_outputs(path: str, Y) -> None:
+    """--dump-outputs: the Y of the last timed step as path/Y.npy (float32).
+    A Y of more than DUMP_MAX_ELEMS elements is sampled: the elements at
+    DUMP_MAX_ELEMS flat indices drawn once from DUMP_SEED (sorted, the same for
+    every run of the same shape), as a 1-D array."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    Y = Y.contiguous()
+    if Y.numel() > DUMP_MAX_ELEMS:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, Y.numel(), DUMP_MAX_ELEMS))
+        Y = Y.view(-1)[torch.from_numpy(idx).to(Y.device)]
+    np.save(os.path.join(path, "Y.npy"), Y.cpu().numpy().astype(np.float32, copy=False))
 
 
 def launch_mode(gpus: int, env) -> str:
@@ -273,14 +311,20 @@ def build_line(a, *, world, mode, backend, M, K, Nr, Ntot, s, nnz, nnz_all, knam
                clock_warmup=(0.0, 0), kernel_timing=None) -> dict:
     """The JSON line rank 0 prints (bench.py contract), from the measured
     quantities (max over ranks).  Pure: tests/test_bench_launch.py checks it
-    without a GPU."""
+    without a GPU.  `kern_ms_max` is None when the kernel alone was not timed
+    (a plain run whose step is two launches): its figures are then null, as
+    are the keys of the legs that only --full runs."""
     flops_all = M * (nnz_all + Ntot)  # sum over ranks of T.flops(M, Nr, nnz_rank)
     value, ms_step = headline(world, a.steps, flops_all, compute_elapsed_max,
                               None if gather is None else gather["pipeline_elapsed_s"])
     alg_bytes = T.algorithmic_bytes(M, Nr, K, nnz)  # per launch, this rank
     adds = T.flops(M, Nr, nnz)                       # per launch: one IEEE add per (m, nonzero) + bias
-    achieved = alg_bytes / (kern_ms_max * 1e-3) / 1e9
-    binding_frac = round(adds / (kern_ms_max * 1e-3) / 1e12 / VALU_PEAK_TADDS, 4)
+
+    def per_kernel_s(q, scale, digits):
+        return None if kern_ms_max is None else round(q / (kern_ms_max * 1e-3) / scale, digits)
+
+    achieved = per_kernel_s(alg_bytes, 1e9, 2)
+    binding_frac = per_kernel_s(adds, 1e12 * VALU_PEAK_TADDS, 4)
     if world == 1:
         workload = "BASELINE configs[2]" if (M, K, Nr, s) == (4096, 4096, 16384, 4) else "custom"
     elif mode == "weak":
@@ -318,31 +362,33 @@ def build_line(a, *, world, mode, backend, M, K, Nr, Ntot, s, nnz, nnz_all, knam
         "config": {"workload": workload, "M": M, "K": K, "N_per_gpu": Nr, "N_total": Ntot, "s": s,
                    "nnz_per_gpu": nnz, "parallelism": f"W columns x{world}"
                    + (" + all-gather of Y" if world > 1 else "")},
-        "roofline": {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBPS,
-                     "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBPS, 5),
+        "full": bool(getattr(a, "full", False)),
+        "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS,
+                     "unit": "GB/s", "frac": per_kernel_s(alg_bytes, 1e9 * HBM_PEAK_GBPS, 5),
                      "traffic": traffic,
-                     "kernel": kname, "kernel_ms": round(kern_ms_max, 4), "kernel_timing": kernel_timing,
+                     "kernel": kname, "kernel_ms": None if kern_ms_max is None else round(kern_ms_max, 4),
+                     "kernel_timing": kernel_timing,
                      "algorithmic_bytes_per_launch": alg_bytes,
-                     "kernel_gflops": round(adds / (kern_ms_max * 1e-3) / 1e9, 2),
+                     "kernel_gflops": per_kernel_s(adds, 1e9, 2),
                      "traffic_source": (os.path.relpath(PROFILE_PMC, REPO) + " (read bytes by request size "
                                         "TCC_EA0_RDREQ_{32,64,128}B + WRITE_SIZE"
                                         + ("; plan asserted)" if plan_asserted else ")")
                                         if traffic is not None else None),
                      "traffic_fetch_size_x2": traffic_fs2,
                      "binding": {"resource": "valu fp32 adds (DESIGN.md 4)", "adds_per_launch": adds,
-                                 "achieved_Tadds": round(adds / (kern_ms_max * 1e-3) / 1e12, 2),
+                                 "achieved_Tadds": per_kernel_s(adds, 1e12, 2),
                                  "peak_Tadds": round(VALU_PEAK_TADDS, 2), "frac": binding_frac}},
         # the roof that binds this kernel, top level so a
         # parser that keeps only flat keys of `roofline` still sees it
         "binding_roof": {"resource": "valu fp32 adds", "frac": binding_frac, "kernel": kname,
-                         "achieved_Tadds": round(adds / (kern_ms_max * 1e-3) / 1e12, 2),
+                         "achieved_Tadds": per_kernel_s(adds, 1e12, 2),
                          "peak_Tadds": round(VALU_PEAK_TADDS, 2)},
         "cpu_baseline": cpu,
         "compute_only": compute_only if world > 1 else None,
         "stream_ms_per_step": None if stream_ms is None else round(stream_ms / a.steps, 4),
         "e2e_host_pointers": e2e,
-        "allgather_ms": None if gather is None else round(gather["allgather_ms"], 3),
-        "allgather_gbps_per_gpu": (None if gather is None else
+        "allgather_ms": None if gather is None or gather["allgather_ms"] is None else round(gather["allgather_ms"], 3),
+        "allgather_gbps_per_gpu": (None if gather is None or gather["allgather_ms"] is None else
                                    round(gather["bytes_received_per_gpu"] / (gather["allgather_ms"] * 1e-3) / 1e9, 2)),
         "with_allgather": gather_info,
         "setup_s": round(setup_s, 2),
@@ -459,19 +505,24 @@ def main():
     elapsed = time.perf_counter() - t_start
     stream_ms = ev0.elapsed_time(ev1)
     step_launches = h.call_launches(X, M)
-    # a second pass of K steps with an event pair around every launch of the
-    # main kernel (tcsc_hip_set_timing): the kernel alone when the step also
-    # stages X^T; reported beside (it includes ~3-5 us of the events' own gap)
-    h.set_timing(True)
-    h.kernel_time(reset=True)
-    for _ in range(a.steps):
-        h.gemm_torch(X, b, Y)
-    torch.cuda.synchronize()
-    pair_ms_total, launches = h.kernel_time(reset=True)
-    h.set_timing(False)
-    pair_ms = pair_ms_total / max(launches, 1)
-    kern_ms_total = stream_ms if step_launches == 1 else pair_ms_total
-    launches = a.steps if step_launches == 1 else launches
+    if world == 1 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, Y)
+    # --full: a second pass of K steps with an event pair around every launch
+    # of the main kernel (tcsc_hip_set_timing): the kernel alone when the step
+    # also stages X^T; reported beside (it includes ~3-5 us of the events' own
+    # gap).  Without it the kernel alone is known only when a step is one launch.
+    pair_ms = kern_ms = -1.0  # not measured
+    if a.full:
+        h.set_timing(True)
+        h.kernel_time(reset=True)
+        for _ in range(a.steps):
+            h.gemm_torch(X, b, Y)
+        torch.cuda.synchronize()
+        pair_ms_total, launches = h.kernel_time(reset=True)
+        h.set_timing(False)
+        pair_ms = kern_ms = pair_ms_total / max(launches, 1)
+    if step_launches == 1:
+        kern_ms = stream_ms / a.steps
 
     # --- world > 1: configs[4]'s whole step = the compute of this rank's
     # column block AND the RCCL all-gather of every rank's block into the
@@ -487,14 +538,16 @@ def main():
         del Yall
         torch.cuda.synchronize()
         barrier()
-        reps = max(3, a.steps // 4)
-        tg = time.perf_counter()
-        for _ in range(reps):
-            Yall = D.allgather_columns(Y, Ntot, world)
-        torch.cuda.synchronize()
-        barrier()
-        ag_s = (time.perf_counter() - tg) / reps
-        del Yall
+        ag_s = -1.0
+        if a.full:  # the gather alone
+            reps = max(3, a.steps // 4)
+            tg = time.perf_counter()
+            for _ in range(reps):
+                Yall = D.allgather_columns(Y, Ntot, world)
+            torch.cuda.synchronize()
+            barrier()
+            ag_s = (time.perf_counter() - tg) / reps
+            del Yall
         pipe = D.GatherPipeline(M, Ntot, world, chunks=a.chunks, device=dev)
         Xc = {(r0, r1): X[r0:r1] for r0, r1 in pipe.ranges}  # row slices: contiguous
 
@@ -513,28 +566,34 @@ def main():
         barrier()
         torch.cuda.synchronize()
         pipe_elapsed = time.perf_counter() - tp
-        # the pipelined Y: this rank's columns equal its compute-only block,
-        # and every other rank's columns carry that rank's block (a checksum
-        # of each block, all-gathered, against the same checksum of Y_full)
-        ok = torch.equal(Yfull[:, n0:n1].view(torch.int32), Y.view(torch.int32))
-        mine = Y.view(torch.int32).to(torch.int64).sum().reshape(1)
-        sums = torch.empty(world, dtype=torch.int64, device=dev)
-        D._all_gather_into(sums, mine)
-        got = torch.stack([Yfull[:, c0:c1].view(torch.int32).to(torch.int64).sum()
-                           for c0, c1 in (D.column_shard(Ntot, world, r) for r in range(world))])
-        blocks_ok = torch.equal(sums, got)
+        if rank == 0 and a.dump_outputs:
+            dump_outputs(a.dump_outputs, Yfull)
+        ok = blocks_ok = True
+        if a.full:
+            # the pipelined Y: this rank's columns equal its compute-only block,
+            # and every other rank's columns carry that rank's block (a checksum
+            # of each block, all-gathered, against the same checksum of Y_full)
+            ok = torch.equal(Yfull[:, n0:n1].view(torch.int32), Y.view(torch.int32))
+            mine = Y.view(torch.int32).to(torch.int64).sum().reshape(1)
+            sums = torch.empty(world, dtype=torch.int64, device=dev)
+            D._all_gather_into(sums, mine)
+            got = torch.stack([Yfull[:, c0:c1].view(torch.int32).to(torch.int64).sum()
+                               for c0, c1 in (D.column_shard(Ntot, world, r) for r in range(world))])
+            blocks_ok = torch.equal(sums, got)
         tg = torch.tensor([ag_s, pipe_elapsed, 0.0 if ok else 1.0, 0.0 if blocks_ok else 1.0],
                           device=dev, dtype=torch.float64)
         dist.all_reduce(tg, op=dist.ReduceOp.MAX)
-        gather = {"allgather_ms": float(tg[0]) * 1e3, "pipeline_elapsed_s": float(tg[1]),
-                  "columns_match": float(tg[2]) == 0.0, "blocks_match": float(tg[3]) == 0.0,
+        gather = {"allgather_ms": float(tg[0]) * 1e3 if a.full else None, "pipeline_elapsed_s": float(tg[1]),
+                  "columns_match": float(tg[2]) == 0.0 if a.full else None,
+                  "blocks_match": float(tg[3]) == 0.0 if a.full else None,
                   "bytes_received_per_gpu": 4 * M * (Ntot - Nr), "chunks": len(pipe.ranges)}
         del pipe, Yfull
 
-    tt = torch.tensor([elapsed, kern_ms_total / max(launches, 1), pair_ms], device=dev, dtype=torch.float64)
+    tt = torch.tensor([elapsed, kern_ms, pair_ms], device=dev, dtype=torch.float64)
     if world > 1:
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-    elapsed_max, kern_ms_max, pair_ms_max = float(tt[0]), float(tt[1]), float(tt[2])
+    elapsed_max = float(tt[0])
+    kern_ms_max, pair_ms_max = (None if float(t) < 0 else float(t) for t in tt[1:])
     nnz_t = torch.tensor([nnz], device=dev, dtype=torch.int64)
     if world > 1:
         dist.all_reduce(nnz_t)
@@ -544,7 +603,7 @@ def main():
     # step, D2H Y; synchronous, as the reference calls it, main.cpp:214-216).
     # PCIe-inclusive, reported beside the headline, never as `value`.
     e2e = None
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and a.full:
         Xh, bh = X.cpu().numpy(), b.cpu().numpy()
         Yh = np.empty((M, Nr), np.float32)
         Yref = Y.cpu().numpy()
@@ -576,7 +635,7 @@ def main():
 
     # --- CPU baseline (rank 0 at N=1 only): bounded samples of the same workload
     cpu = None
-    if rank == 0 and world == 1 and a.cpu_rows > 0:
+    if rank == 0 and world == 1 and a.full and a.cpu_rows > 0:
         cpu = cpu_baseline(X, csp, csn, rip, rin, K, Nr, s, Y, a.cpu_rows)
 
     if rank == 0:
@@ -607,8 +666,9 @@ def main():
                                         "kernel_ms_source": ("HIP events on the kernel's stream over the timed "
                                                              "region / K (one launch per step, back to back)"
                                                              if step_launches == 1 else
-                                                             "HIP event pair around every launch, second pass"),
-                                        "event_pair_kernel_ms": round(pair_ms_max, 4)})
+                                                             "HIP event pair around every launch, second pass"
+                                                             if a.full else "not measured (--full)"),
+                                        "event_pair_kernel_ms": None if pair_ms_max is None else round(pair_ms_max, 4)})
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()

@@ -15,10 +15,11 @@ TSG_REF_PERF_OUT=gpurun_out/ref_perf_$TAG.txt timeout -k 10 900 python -u -m pyt
 rc=$?; echo "pytest rc=$rc: $(tail -1 gpurun_out/pytest_$TAG.log)"; [ $rc -eq 0 ] || { grep -E "FAIL|Error" gpurun_out/pytest_$TAG.log | head -20; tail -30 gpurun_out/pytest_$TAG.log; exit $rc; }
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/smoke_$TAG.log 2>&1
 rc=$?; echo "smoke rc=$rc"; [ $rc -eq 0 ] || { tail -20 gpurun_out/smoke_$TAG.log; exit $rc; }
-timeout -k 10 300 python bench.py > gpurun_out/bench_$TAG.jsonl 2> gpurun_out/bench_$TAG.err
-rc=$?; echo "bench rc=$rc"; [ $rc -eq 0 ] || { tail -20 gpurun_out/bench_$TAG.err; exit $rc; }
-tail -1 gpurun_out/bench_$TAG.jsonl | cut -c1-300
-TSG_BENCH_BACKEND=gloo timeout -k 10 400 python bench.py --gpus 8 --M 512 --steps 3 --timeout 350 \
-    > gpurun_out/bench_gloo8_$TAG.jsonl 2> gpurun_out/bench_gloo8_$TAG.err
-rc=$?; echo "gloo8 rc=$rc"; [ $rc -eq 0 ] || { tail -20 gpurun_out/bench_gloo8_$TAG.err; exit $rc; }
-tail -1 gpurun_out/bench_gloo8_$TAG.jsonl | cut -c1-300
+BENCH_OUT=${BENCH_OUT:-bench_out}; mkdir -p "$BENCH_OUT"  # the bench lines of this script
+timeout -k 10 300 python bench.py --full > "$BENCH_OUT"/bench_$TAG.jsonl 2> "$BENCH_OUT"/bench_$TAG.err
+rc=$?; echo "bench rc=$rc"; [ $rc -eq 0 ] || { tail -20 "$BENCH_OUT"/bench_$TAG.err; exit $rc; }
+tail -1 "$BENCH_OUT"/bench_$TAG.jsonl | cut -c1-300
+TSG_BENCH_BACKEND=gloo timeout -k 10 400 python bench.py --full --gpus 8 --M 512 --steps 3 --timeout 350 \
+    > "$BENCH_OUT"/bench_gloo8_$TAG.jsonl 2> "$BENCH_OUT"/bench_gloo8_$TAG.err
+rc=$?; echo "gloo8 rc=$rc"; [ $rc -eq 0 ] || { tail -20 "$BENCH_OUT"/bench_gloo8_$TAG.err; exit $rc; }
+tail -1 "$BENCH_OUT"/bench_gloo8_$TAG.jsonl | cut -c1-300

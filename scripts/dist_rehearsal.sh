@@ -8,14 +8,15 @@
 # NPROC=4 (default 2) rehearses 4 ranks; MODES="weak" limits the modes.
 set -o pipefail
 export TMPDIR=/tmp TSG_BENCH_BACKEND=gloo
-mkdir -p gpurun_out
+BENCH_OUT=${BENCH_OUT:-bench_out}; mkdir -p "$BENCH_OUT"
 NPROC=${NPROC:-2}
 for mode in ${MODES:-weak strong}; do
   extra=""; [ $mode = strong ] && extra="--strong"
+  log="$BENCH_OUT"/dist_rehearsal_${mode}_$NPROC.log
   timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node $NPROC --master-addr 127.0.0.1 \
-      --master-port 29517 bench.py --gpus $NPROC --steps 5 --warmup 2 $extra > gpurun_out/dist_rehearsal_${mode}_$NPROC.log 2>&1
-  rc=$?; echo "rehearsal $mode rc=$rc"; [ $rc -eq 0 ] || { tail -20 gpurun_out/dist_rehearsal_${mode}_$NPROC.log; exit $rc; }
-  python3 - gpurun_out/dist_rehearsal_${mode}_$NPROC.log <<'P'
+      --master-port 29517 bench.py --full --gpus $NPROC --steps 5 --warmup 2 $extra > $log 2>&1
+  rc=$?; echo "rehearsal $mode rc=$rc"; [ $rc -eq 0 ] || { tail -20 $log; exit $rc; }
+  python3 - $log <<'P'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])
 print(sys.argv[1], "scaling", d["scaling"], "value", d["value"], "allgather_ms", d["allgather_ms"],

@@ -7,7 +7,7 @@ OUT=gpurun_out/knobs_${1:-x}.txt; shift || true
 : > $OUT
 for rep in 1 2; do
   for v in "$@"; do
-    env $(echo "$v" | tr '|' ' ') timeout -k 10 120 python bench.py --steps 30 --warmup 3 --cpu-rows 0 > /tmp/ab.log 2>&1 || { echo "$v failed"; tail -3 /tmp/ab.log; exit 1; }
+    env $(echo "$v" | tr '|' ' ') timeout -k 10 120 python bench.py --full --steps 30 --warmup 3 --cpu-rows 0 > /tmp/ab.log 2>&1 || { echo "$v failed"; tail -3 /tmp/ab.log; exit 1; }
     python3 - "$v" "$rep" >> $OUT <<'P'
 import json, sys
 d = json.loads([l for l in open("/tmp/ab.log") if l.startswith("{")][-1])

@@ -6,7 +6,7 @@ mkdir -p gpurun_out
 OUT=gpurun_out/m_rounds_${1:-x}.txt; : > $OUT
 for rep in 1 2; do
   for M in 1024 2048 3072 4096 6144 8192; do
-    timeout -k 10 120 python bench.py --M $M --steps 20 --warmup 3 --cpu-rows 0 > /tmp/mr.log 2>&1 || { echo "M=$M failed"; tail -3 /tmp/mr.log; exit 1; }
+    timeout -k 10 120 python bench.py --full --M $M --steps 20 --warmup 3 --cpu-rows 0 > /tmp/mr.log 2>&1 || { echo "M=$M failed"; tail -3 /tmp/mr.log; exit 1; }
     python3 - $M $rep >> $OUT <<'P'
 import json, sys
 d = json.loads([l for l in open("/tmp/mr.log") if l.startswith("{")][-1])

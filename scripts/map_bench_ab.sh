@@ -15,7 +15,7 @@ for rep in 1 2 3; do
       if [ "$v" != default ]; then
         if [[ "$v" == *=* ]]; then IFS=',' read -ra envs <<< "$v"; else envs=("TSG_LIB=ternary-spgemm_amd/$v/libternary_spgemm.so"); fi
       fi
-      env "${envs[@]}" timeout -k 10 200 python bench.py --M $M --K $K --N $N --steps 10 --warmup 2 --cpu-rows 0 > /tmp/mb.log 2>&1 || { echo "$v $sh failed"; tail -3 /tmp/mb.log; exit 1; }
+      env "${envs[@]}" timeout -k 10 200 python bench.py --full --M $M --K $K --N $N --steps 10 --warmup 2 --cpu-rows 0 > /tmp/mb.log 2>&1 || { echo "$v $sh failed"; tail -3 /tmp/mb.log; exit 1; }
       python3 - $rep $v $sh >> "$OUT" <<'P'
 import json, sys
 d = json.loads([l for l in open("/tmp/mb.log") if l.startswith("{")][-1])

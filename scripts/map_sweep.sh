@@ -8,7 +8,7 @@ OUT=gpurun_out/map_sweep_$TAG.txt; : > $OUT
 for M in $MS; do
   for v in "$@"; do
     unset TSG_LIB; [ "$v" = default ] || export TSG_LIB=ternary-spgemm_amd/$v/libternary_spgemm.so
-    timeout -k 10 120 python bench.py --M $M --steps 20 --warmup 3 --cpu-rows 0 > /tmp/ms.log 2>&1 || { echo "$v M=$M failed"; tail -3 /tmp/ms.log; exit 1; }
+    timeout -k 10 120 python bench.py --full --M $M --steps 20 --warmup 3 --cpu-rows 0 > /tmp/ms.log 2>&1 || { echo "$v M=$M failed"; tail -3 /tmp/ms.log; exit 1; }
     python3 - $M $v >> $OUT <<'P'
 import json, sys
 d = json.loads([l for l in open("/tmp/ms.log") if l.startswith("{")][-1])

@@ -9,7 +9,7 @@ OUT=gpurun_out/transpose_ab_$TAG.txt; mkdir -p gpurun_out; : > $OUT
 for rep in 1 2 3; do
   for v in default lds; do
     unset TSG_TRANSPOSE; [ $v = default ] || export TSG_TRANSPOSE=$v
-    timeout -k 10 120 python bench.py --steps 40 --cpu-rows 0 > /tmp/tab.log 2>&1 || { echo "$v failed"; tail -3 /tmp/tab.log; exit 1; }
+    timeout -k 10 120 python bench.py --full --steps 40 --cpu-rows 0 > /tmp/tab.log 2>&1 || { echo "$v failed"; tail -3 /tmp/tab.log; exit 1; }
     python3 - $rep $v >> $OUT <<'P'
 import json, sys
 d = json.loads([l for l in open("/tmp/tab.log") if l.startswith("{")][-1])

@@ -11,6 +11,28 @@ for p in (os.path.join(REPO, "oracle"), os.path.join(REPO, "ternary-spgemm_amd")
 GOLDEN = os.path.join(REPO, "tests", "golden")
 
 
+class _GoldenSmall:
+    """tests/golden/ref_small*.npz (make_golden.py writes the vectors in parts,
+    each under 1 MiB) read as one archive: `.files` and `[key]` as np.load gives."""
+
+    def __init__(self):
+        import glob
+        import numpy as np
+        self._parts = [np.load(p) for p in sorted(glob.glob(os.path.join(GOLDEN, "ref_small*.npz")))]
+        self.files = [k for z in self._parts for k in z.files]
+        assert len(set(self.files)) == len(self.files)
+
+    def __getitem__(self, key):
+        for z in self._parts:
+            if key in z.files:
+                return z[key]
+        raise KeyError(key)
+
+
+def load_golden_small():
+    return _GoldenSmall()
+
+
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs an MI355X (gfx950) GPU; runs through the C-ABI")
     config.addinivalue_line("markers", "slow: long-running CPU case")

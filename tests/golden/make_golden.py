@@ -109,7 +109,25 @@ def small_cases():
             p + "Xfrac": Xf, p + "Yfrac_oracle": Yf, p + "Yfrac_prelu_oracle": Ypf,
         })
         print("case", i, (M, K, N, s, seed), "nnz", len(rip) + len(rin))
-    np.savez_compressed(os.path.join(HERE, "ref_small.npz"), **out)
+    save_small(out)
+
+
+# ref_small*.npz: the vectors in parts, each file under 1 MiB (conftest.load_golden_small
+# reads them back as one archive).  Part "" holds the cases not named here.
+SMALL_PARTS = {
+    "_c5a": ["c5_shape", "c5_Wpos_bits", "c5_Wneg_bits", "c5_sha256_tcsc", "c5_ds_bytes", "c5_X", "c5_b", "c5_alpha"],
+    "_c5b": ["c5_Y_ref_gemm", "c5_Y_ref_gemm_prelu", "c5_Xfrac"],
+    "_c5c": ["c5_Yfrac_oracle", "c5_Yfrac_prelu_oracle"],
+}
+
+
+def save_small(out):
+    named = {k for keys in SMALL_PARTS.values() for k in keys}
+    parts = dict(SMALL_PARTS, **{"": [k for k in out if k not in named]})
+    for tag, keys in parts.items():
+        path = os.path.join(HERE, f"ref_small{tag}.npz")
+        np.savez_compressed(path, **{k: out[k] for k in keys})
+        assert os.path.getsize(path) < 1 << 20, path
 
 
 def hashed_configs():

@@ -144,3 +144,49 @@ def test_line_world1_is_the_compute_step():
     assert ln["ms_per_step"] == 1.23 and ln["compute_only"] is None and ln["with_allgather"] is None
     assert ln["config"]["workload"] == "BASELINE configs[2]"
     assert ln["binding_roof"]["frac"] == ln["roofline"]["binding"]["frac"]
+    assert ln["full"] is False and ln["cpu_baseline"] is None and ln["e2e_host_pointers"] is None
+
+
+def test_line_without_the_kernel_alone():
+    """A plain run (no --full) of a two-launch step has not timed the kernel
+    alone: the headline is unchanged and the kernel's own figures are null."""
+    sys.path.insert(0, REPO)
+    import bench
+    M, K, Nr, s = 4096, 4096, 16384, 4
+    nnz = K * Nr // s
+    kw = dict(world=1, mode="weak", backend=None, M=M, K=K, Nr=Nr, Ntot=Nr, s=s, nnz=nnz, nnz_all=nnz,
+              kname="tsg_jit_kernel", compute_elapsed_max=20 * 1.23e-3)
+    ln = bench.build_line(_args(), kern_ms_max=None, **kw)
+    ref = bench.build_line(_args(), kern_ms_max=1.22, **kw)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps"):
+        assert ln[k] == ref[k]
+    assert ln["ms_per_step"] == 1.23
+    assert ln["roofline"]["kernel_ms"] is None and ln["roofline"]["achieved"] is None
+    assert ln["roofline"]["binding"]["frac"] is None and ln["binding_roof"]["frac"] is None
+    assert ref["roofline"]["kernel_ms"] == 1.22 and 0 < ref["binding_roof"]["frac"] < 1
+    # world > 1 without --full: the gather alone and the block checks are not run
+    gather = {"allgather_ms": None, "pipeline_elapsed_s": 20 * 3.1e-3, "columns_match": None, "blocks_match": None,
+              "bytes_received_per_gpu": 4 * M * Nr, "chunks": 4}
+    ln2 = bench.build_line(_args(), kern_ms_max=1.22, gather=gather, **dict(kw, world=2, backend="nccl", Ntot=2 * Nr,
+                                                                               nnz_all=2 * nnz))
+    assert ln2["ms_per_step"] == 3.1 and ln2["allgather_ms"] is None and ln2["allgather_gbps_per_gpu"] is None
+
+
+def test_dump_outputs(tmp_path, monkeypatch):
+    """--dump-outputs: a small Y is written whole, a large one as the same
+    seeded sample of its elements on every run, always float32."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, REPO)
+    import bench
+    Y = torch.arange(7 * 13, dtype=torch.float32).reshape(7, 13) * 0.5
+    bench.dump_outputs(str(tmp_path / "a"), Y)
+    got = np.load(tmp_path / "a" / "Y.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, Y.numpy())
+    monkeypatch.setattr(bench, "DUMP_MAX_ELEMS", 40)
+    bench.dump_outputs(str(tmp_path / "b"), Y)
+    bench.dump_outputs(str(tmp_path / "c"), Y + 1)
+    sb, sc = np.load(tmp_path / "b" / "Y.npy"), np.load(tmp_path / "c" / "Y.npy")
+    assert sb.dtype == np.float32 and sb.shape == (40,)
+    assert np.array_equal(sc, sb + 1)  # the same elements both times
+    assert set(sb.tolist()) <= set(Y.flatten().tolist()) and len(set(sb.tolist())) > 10

@@ -11,7 +11,7 @@ import os
 import numpy as np
 import pytest
 
-from conftest import GOLDEN
+from conftest import GOLDEN, load_golden_small
 
 pytestmark = pytest.mark.gpu
 
@@ -27,7 +27,7 @@ def _bits_eq(a, b):
 
 @pytest.fixture(scope="module")
 def small():
-    return np.load(os.path.join(GOLDEN, "ref_small.npz"))
+    return load_golden_small()
 
 
 def _case_prefixes(z):

@@ -12,7 +12,7 @@ import os
 import numpy as np
 import pytest
 
-from conftest import GOLDEN
+from conftest import GOLDEN, load_golden_small
 
 
 def _sha(*arrays) -> str:
@@ -20,7 +20,7 @@ def _sha(*arrays) -> str:
 
 
 def _load_small():
-    return np.load(os.path.join(GOLDEN, "ref_small.npz"))
+    return load_golden_small()
 
 
 def _case_ids(z):
