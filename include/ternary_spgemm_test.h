@@ -35,7 +35,8 @@ int64_t tcsc_hip_call_image_bytes(tsg_tcsc *h, int M);
  * 64 is the default; small-M calls use narrower streams (32, 16, 8) so more
  * workgroups fill the GPU -- each width is its own code image, compiled on the
  * first call (or tcsc_hip_reserve) that picks it.  Same results bit for bit.
- * tcsc_hip_jit_width: the width a call with M rows runs (0: not a jit handle).
+ * tcsc_hip_jit_width: the width a call with M rows runs (0: not a jit handle,
+ * or a call the small-M walk takes).
  * tcsc_hip_set_jit_width: 0 = automatic (default), or pin 64/32/16/8, or
  * 128 (the 64-row image only: pinning it selects that image; BlockedTCSC: 64
  * only).  Extension: no reference counterpart. */

@@ -7,7 +7,7 @@ One JSON object per shape on stdout.
     python scripts/configs.py [--steps 10] [--all-widths]
 
 --all-widths times every jit stream width (64/32/16/8) per shape, besides the
-automatic pick, to check tsg_capi.cpp pick_jit_width.
+automatic pick, to check tsg_plan.cpp pick_jit_shape.
 """
 import argparse
 import json

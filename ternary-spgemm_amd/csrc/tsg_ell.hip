@@ -662,7 +662,7 @@ namespace {
 // 42.2 us, K = N = 4096 13.5 vs 14.2 us); else 32 (M = 2 at N = 16384, 512
 // workgroups: 20.0 vs 26.4 us with E = 64; profiles/r02_pc_phase_ab.txt).
 // TSG_ELL_PC_E=16/32/64 forces one (A/B sweeps; 32 when the forced ring does
-// not fit).  Availability (tsg_capi.cpp ell_pc_available) is judged at E = 32.
+// not fit).  Availability (tsg_plan.cpp ell_pc_available) is judged at E = 32.
 int pc_phase(int M, int N, int C)
 {
     static const int env = [] {

@@ -95,7 +95,7 @@ constexpr uint32_t kJitFormat = 2;                      // region header word 7 
 // subtracts (piece & 3) KiB from its per-piece global offsets
 constexpr uint32_t kJitM0kFlag = 1u << 16;
 // region header word 7 bit 17: the far-X^T image -- no code touches, X^T
-// staged with non-temporal loads (tsg_capi.cpp far_xt)
+// staged with non-temporal loads (tsg_plan.cpp far_xt)
 constexpr uint32_t kJitFarFlag = 1u << 17;
 
 // The 64-row image (round 4): one M row per lane, 64-row M
@@ -174,7 +174,7 @@ constexpr uint32_t kJit64HalfFlag = 1u << 19;
 // Stream width: columns per generated stream.  kJitNW (64) is the default;
 // narrower streams (32, 16, 8: same register contract, fewer accumulators,
 // dispatcher lib/tsg_jit_w<nw>.co) give small-M calls more workgroups
-// (tsg_capi.cpp pick_jit_width).  BlockedTCSC runs at kJitNW only.
+// (tsg_plan.cpp pick_jit_shape).  BlockedTCSC runs at kJitNW only.
 constexpr int kJitWidths[] = {kJitNW, 32, 16, 8};
 inline bool jit_width_ok(int nw) { return nw == kJitNW || nw == 32 || nw == 16 || nw == 8; }
 // waves per workgroup: 8, or 4 for the narrow widths (lib/tsg_jit_w<nw>_4w.co):

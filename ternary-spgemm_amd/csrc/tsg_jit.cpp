@@ -124,7 +124,7 @@ struct Emit {
     }
     // s[88:89] = s[90:91] + off: s[90:91] is the touch base the dispatcher
     // sets per call -- the region base, or 8 KiB below it (the touches then
-    // cover the code from the step's own position, tsg_capi.cpp tnear)
+    // cover the code from the step's own position, tsg_plan.cpp pick_tnear)
     void touch_addr(uint32_t region_off)
     {
         align8();
@@ -456,7 +456,7 @@ void build_jit_code(const int32_t *csp, const int32_t *csn, const int32_t *rip, 
         E.dma_cp = a & 0x2030000u;
         E.touch_cp = t & 0x2030000u;
     }
-    // far-X^T image (tsg_capi.cpp far_xt): X^T staged non-temporally so its
+    // far-X^T image (tsg_plan.cpp far_xt): X^T staged non-temporally so its
     // stream does not evict the code from the Infinity Cache, and no code
     // touches
     if (far) E.dma_cp |= 0x20000u;
@@ -477,7 +477,7 @@ void build_jit_code(const int32_t *csp, const int32_t *csn, const int32_t *rip, 
     // code-prefetch window: TSG_JIT_TOUCH="first,count" in 8-KiB units (default
     // 1,1), relative to the touch base s[90:91]: the dispatcher moves it 8 KiB
     // back per call (the window then starts at the step's own position) where
-    // that pays (tsg_capi.cpp pick_tnear)
+    // that pays (tsg_plan.cpp pick_tnear)
     uint32_t touch_first = 1, touch_count = 1;
     if (const char *tv = knob_value("TSG_JIT_TOUCH")) std::sscanf(tv, "%u,%u", &touch_first, &touch_count);
     if (touch_count > 4) touch_count = 4;
@@ -761,7 +761,7 @@ void build_jit_code(const int32_t *csp, const int32_t *csn, const int32_t *rip, 
                 // next step
                 // (lv: the lane-offset VGPR -- v[lane128] for the step's own
                 // touch, v[lane128 + 1] for the per-group ones: the dispatcher
-                // zeroes the latter per call, one line then, tsg_capi.cpp xtouch)
+                // zeroes the latter per call, one line then, tsg_plan.cpp pick_xtouch)
                 auto touches = [&](uint32_t lv) {
                     if (rolling) {
                         const uint32_t pos = E.pos_bytes();

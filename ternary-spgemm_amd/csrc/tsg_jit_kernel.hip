@@ -206,7 +206,7 @@ extern "C" __global__ __launch_bounds__(kJThreads, kJHalf ? 2 : 1) void TSG_JIT_
     }
 
     // tile map (tsg_jit_map.h): gn column tiles x gm M tiles per XCD group,
-    // chosen per call by the host (tsg_capi.cpp pick_jit_map)
+    // chosen per call by the host (tsg_plan.cpp pick_jit_map)
     int nt, mt;
     tsg_jit_tile(blockIdx.x, mtiles, ntiles, gn, gm, nt, mt);
     const int m0 = mt * kJTileM;
@@ -271,7 +271,7 @@ extern "C" __global__ __launch_bounds__(kJThreads, kJHalf ? 2 : 1) void TSG_JIT_
     // code touch (one dword per 128-B line of the stream ahead, into L2): only
     // workgroups with (mt & tmask) == 0 spread it over the lines; the others
     // load one line 64 times (one request) -- the M tiles that run the same
-    // stream share what one of them touched (tsg_capi.cpp pick_jit_map)
+    // stream share what one of them touched (tsg_plan.cpp pick_jit_map)
     const uint32_t l128 = (mt & tmask) == 0 ? (uint32_t)lane * 128u : 0u;
     // the generated code's per-group touches (round 6) use v[lane128 + 1]:
     // the same lines where the call wants them (xtouch), else one line

@@ -1,6 +1,6 @@
 // tsg_jit_map.h -- workgroup -> (column tile, M tile) map of the weight-compiled
 // kernel, shared by the dispatcher (tsg_jit_kernel.hip) and the host (the
-// per-call choice of gn/gm in tsg_capi.cpp, and the bijection test through
+// per-call choice of gn/gm in tsg_plan.cpp, and the bijection test through
 // tsg_jit_tile_map).
 //
 // XCD-aware: workgroup ids are dealt to the 8 XCDs round-robin (id L runs on

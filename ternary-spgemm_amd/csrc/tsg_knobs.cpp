@@ -76,7 +76,7 @@ bool cp_ok(const char *v)
 }
 
 // TSG_JIT_TOUCH = "first,count" in 8-KiB units, first >= 1 (the dispatcher may
-// move the touch base 8 KiB back, tsg_capi.cpp pick_tnear), count <= 4, inside
+// move the touch base 8 KiB back, tsg_plan.cpp pick_tnear), count <= 4, inside
 // the tail padding
 bool touch_ok(const char *v)
 {

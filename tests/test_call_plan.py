@@ -46,7 +46,7 @@ import pytest
     # the 128-row image's whole-round shapes now lose on the step too (its X^T pass; r05z_n512_ab.jsonl)
     ((64000, 4096, 512, 4), dict(kernel="tsg_jit64_kernel", width=64, waves=8, far=False, map=(1, 8), tmask=0)),
     # the 64-row image at mid M (round 4, r04d_rows64_ab.jsonl): one round of workgroups,
-    # the shape of least modelled time (tsg_capi.cpp pick_jit_shape)
+    # the shape of least modelled time (tsg_plan.cpp pick_jit_shape)
     ((256, 4096, 16384, 4), dict(kernel="tsg_jit64_kernel", width=32, waves=8, far=False, map=(4, 4), tmask=3)),
     ((512, 4096, 16384, 4), dict(kernel="tsg_jit64_kernel", width=64, waves=8, far=False, map=(4, 8), tmask=3)),
     ((128, 4096, 16384, 4), dict(kernel="tsg_jit64_kernel", width=16, waves=8, far=False, map=(4, 2), tmask=0)),  # 87.1 vs 32 x 4 91-97 us
@@ -193,7 +193,7 @@ def test_plan_staged_image_rules(tsg, M, K, N, kernel):
 
 
 @pytest.mark.parametrize("M,K,N,s,on", [
-    # the per-group code touches spread (tsg_capi.cpp pick_xtouch; profiles/r06h_tgroup_longk_ab.jsonl)
+    # the per-group code touches spread (tsg_plan.cpp pick_xtouch; profiles/r06h_tgroup_longk_ab.jsonl)
     (4096, 4096, 16384, 4, True),     # configs[2] 1157 vs 1221 us
     (4096, 4096, 16384, 2, True),     # s = 2 2177 vs 2309
     (4096, 16384, 4096, 4, True),     # 1115 vs 1192

@@ -52,7 +52,7 @@ def test_full_y_integer_x(tsg, M, K, N, s):
     b = torch.full((N,), 2.0, device=dev)  # main.cpp:194
     Y = h.gemm_torch(X, b)
     kernel = h.call_kernel(M) + (" (far-X^T image)" if h.call_far(M) else "")
-    # round 5: no automatic call takes the far-X^T image (the 64-row image wins, tsg_capi.cpp
+    # round 5: no automatic call takes the far-X^T image (the 64-row image wins, tsg_plan.cpp
     # pick_rows64); the 128-row image pinned takes it at the largest case (far_xt)
     assert not h.call_far(M)
     W = _dense_w(csp, csn, rip, rin, K, N, dev)

@@ -19,7 +19,7 @@ SMALL = ("tsg_tcsc_ell_kernel", "tsg_tcsc_ell_pc_kernel")
 def _small_kernel(M, K, N, mode):
     """The kernel tcsc_hip_set_small_m(mode) sends a call with M rows to:
     1-row producer/consumer tiles for M = 1, and for M <= 4 while M * N <=
-    32768, when K fits the 1-row tile's LDS chunk (tsg_capi.cpp
+    32768, when K fits the 1-row tile's LDS chunk (tsg_plan.cpp
     pick_ell_variant)."""
     # (the 1-row tile's chunk holds K <= 40956; with the producer/consumer ring
     # beside it in 160 KiB of LDS, K <= 34812: tsg_ell.hip pc_lds)

@@ -413,7 +413,7 @@ def test_jit_code_emulates_base_tcsc(tsg, oracle_mod, M, K, N, s):
 @pytest.mark.parametrize("width", [32, 16, 8])
 @pytest.mark.parametrize("M,K,N,s", [(5, 70, 33, 2), (130, 200, 150, 4), (3, 97, 9, 16)])
 def test_jit_code_narrow_streams(tsg, oracle_mod, M, K, N, s, width):
-    """Narrow streams (small-M widths, tsg_capi.cpp pick_jit_width): same
+    """Narrow streams (small-M widths, tsg_plan.cpp pick_jit_shape): same
     register contract, fewer accumulators, more column tiles; same order."""
     for frac in (False, True):
         _check(tsg, oracle_mod, M, K, N, s, 5 + K + N + width, frac, width=width)
