@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define TSG_ABI_VERSION 1
+#define TSG_ABI_VERSION 2
 
 enum tsg_status {
     TSG_OK = 0,
@@ -141,6 +141,22 @@ int tcsc_hip_gemm_prelu(tsg_tcsc *h, const float *X, const float *b, const float
                         float *Y, int M, int N, int K);
 int tcsc_hip_gemm_prelu_dev(tsg_tcsc *h, const float *dX, const float *db, const float *dalpha,
                             float *dY, int M, int N, int K, void *stream);
+
+/* The same two calls with an output row stride: row m of the result starts at
+ * dY + m * ldY (ldY in floats, 64-bit), so an [M, N] block lands in its own
+ * columns of a wider row-major buffer -- several handles fed by one X writing
+ * side by side, or one column shard of a larger Y -- without a second pass.
+ * ldY >= N is required: a smaller value returns TSG_ERR_ARG with a message and
+ * enqueues nothing.  Floats outside [m * ldY, m * ldY + N) are never written.
+ * Rows whose start is not 16-byte aligned (an odd ldY, a misaligned dY) are
+ * stored float by float, the others with 16-byte stores; the result is the
+ * same bit for bit.  Everything else -- stream semantics, reserve and graph
+ * capture, the kernel an M picks -- is as tcsc_hip_gemm_dev, which is the
+ * ldY = N case of this call.  Extension: no reference counterpart. */
+int tcsc_hip_gemm_dev_ld(tsg_tcsc *h, const float *dX, const float *db, float *dY, int64_t ldY,
+                         int M, int N, int K, void *stream);
+int tcsc_hip_gemm_prelu_dev_ld(tsg_tcsc *h, const float *dX, const float *db, const float *dalpha,
+                               float *dY, int64_t ldY, int M, int N, int K, void *stream);
 
 /* Pre-allocates the per-handle work buffer for row counts up to max_M and, on
  * the weight-compiled kernel, compiles every code image a call with M <= max_M

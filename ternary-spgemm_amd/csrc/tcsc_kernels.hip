@@ -275,7 +275,7 @@ template <bool PRELU>
 __global__ __launch_bounds__(kRxWaves * 64, 8 / kRxWaves) void tsg_tcsc_rx_kernel(
     const float *__restrict__ XT, int Mp, const uint32_t *__restrict__ wstart,
     const uint32_t *__restrict__ ent, const float *__restrict__ b, const float *__restrict__ alpha,
-    float *__restrict__ Y, int M, int N, int nch, int mtiles, int ntiles)
+    float *__restrict__ Y, int64_t ldY, int M, int N, int nch, int mtiles, int ntiles)
 {
     __shared__ __attribute__((aligned(16))) char lds[kRxLdsBytes];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -321,7 +321,7 @@ __global__ __launch_bounds__(kRxWaves * 64, 8 / kRxWaves) void tsg_tcsc_rx_kerne
     for (int r = 0; r < 4; r++) {
         const int m = m0 + 4 * lane + r;
         if (m >= M) continue;
-        float *yrow = Y + (size_t)m * N + ncol0;
+        float *yrow = Y + (size_t)m * (size_t)ldY + ncol0;  // ldY >= N floats per Y row
         float v[kRxNW];
 #pragma unroll
         for (int c = 0; c < kRxNW; c++) {
@@ -405,17 +405,17 @@ int launch_transpose_quads(const float *X, float *XQ, int M, int K, int Mp, int 
 }
 
 int launch_tcsc_rx(const float *XT, int Mp, const uint32_t *wstart, const uint32_t *ent,
-                   const float *b, const float *alpha, float *Y, int M, int N, int Npad, int nch,
+                   const float *b, const float *alpha, float *Y, int64_t ldY, int M, int N, int Npad, int nch,
                    int prelu, void *stream)
 {
     hipStream_t s = (hipStream_t)stream;
     const int mtiles = Mp / kRxTileM, ntiles = Npad / kRxTileCols;
     const dim3 grid((unsigned)(mtiles * ntiles)), block(kRxWaves * kLanes);
     if (prelu)
-        hipLaunchKernelGGL((tsg_tcsc_rx_kernel<true>), grid, block, 0, s, XT, Mp, wstart, ent, b, alpha, Y, M,
+        hipLaunchKernelGGL((tsg_tcsc_rx_kernel<true>), grid, block, 0, s, XT, Mp, wstart, ent, b, alpha, Y, ldY, M,
                            N, nch, mtiles, ntiles);
     else
-        hipLaunchKernelGGL((tsg_tcsc_rx_kernel<false>), grid, block, 0, s, XT, Mp, wstart, ent, b, alpha, Y, M,
+        hipLaunchKernelGGL((tsg_tcsc_rx_kernel<false>), grid, block, 0, s, XT, Mp, wstart, ent, b, alpha, Y, ldY, M,
                            N, nch, mtiles, ntiles);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }

@@ -399,6 +399,7 @@ int ensure_ell(tsg_tcsc *h, int v)
 struct Call {
     const float *dX, *db, *dalpha;
     float *dY;
+    int64_t ldY;  // floats from one Y row to the next (>= N)
     int M;
     hipStream_t s;
     bool prelu, capturing;
@@ -444,10 +445,10 @@ int run_ell(tsg_tcsc *h, const CallPlan &p, const Call &c)
     const tsg_tcsc::EllVariant &e = h->ell[p.ell];
     const int N = h->plan.N, K = h->plan.K;
     const int lrc = p.kernel == Kernel::kEllPc
-                        ? tsg::launch_tcsc_ell_pc(p.ell, c.dX, e.d_ent, e.d_tab, c.db, c.dalpha, c.dY, c.M, N, K, e.img.C,
-                                                  e.img.nch, c.prelu ? 1 : 0, c.s)
-                        : tsg::launch_tcsc_ell(p.ell, c.dX, e.d_ent, e.d_tab, c.db, c.dalpha, c.dY, c.M, N, K, e.img.C,
-                                               e.img.nch, e.img.xb, e.img.zr, c.prelu ? 1 : 0, c.s);
+                        ? tsg::launch_tcsc_ell_pc(p.ell, c.dX, e.d_ent, e.d_tab, c.db, c.dalpha, c.dY, c.ldY, c.M, N, K,
+                                                  e.img.C, e.img.nch, c.prelu ? 1 : 0, c.s)
+                        : tsg::launch_tcsc_ell(p.ell, c.dX, e.d_ent, e.d_tab, c.db, c.dalpha, c.dY, c.ldY, c.M, N, K,
+                                               e.img.C, e.img.nch, e.img.xb, e.img.zr, c.prelu ? 1 : 0, c.s);
     if (lrc != 0)
         return fail(TSG_ERR_HIP, std::string("small-M kernel launch: ") + hipGetErrorString(hipGetLastError()));
     return timing_end(h, slot, c.s);
@@ -469,7 +470,7 @@ int run_rx(tsg_tcsc *h, const CallPlan &p, const Call &c)
     int slot;
     rc = timing_begin(h, c.capturing, c.s, slot);
     if (rc) return rc;
-    if (tsg::launch_tcsc_rx(h->d_work, d.Mp, h->d_seg, h->d_ent, c.db, c.dalpha, c.dY, c.M, N, h->rimg.Npad,
+    if (tsg::launch_tcsc_rx(h->d_work, d.Mp, h->d_seg, h->d_ent, c.db, c.dalpha, c.dY, c.ldY, c.M, N, h->rimg.Npad,
                             h->rimg.nch, c.prelu ? 1 : 0, c.s) != 0)
         return fail(TSG_ERR_HIP, std::string("tcsc launch: ") + hipGetErrorString(hipGetLastError()));
     rc = timing_end(h, slot, c.s);
@@ -515,16 +516,16 @@ int run_jit(tsg_tcsc *h, const CallPlan &p, const tsg_tcsc::JitVariant &jv, cons
     int slot;
     rc = timing_begin(h, c.capturing, c.s, slot);
     if (rc) return rc;
-    if (tsg::launch_tcsc_jit(jv.mod, direct ? c.dX : h->d_work, d.Mp, jv.d_wcode, c.db, c.dalpha, c.dY, c.M, N, jv.Npad,
-                             jv.nch, c.prelu ? 1 : 0, h->d_status, jv.nw * jv.waves, waves, p.gn, p.gm, p.tmask, c.s,
-                             p.tile_m, direct ? K : 0, lastadj, p.xtouch, p.tnear) != 0)
+    if (tsg::launch_tcsc_jit(jv.mod, direct ? c.dX : h->d_work, d.Mp, jv.d_wcode, c.db, c.dalpha, c.dY, c.ldY, c.M, N,
+                             jv.Npad, jv.nch, c.prelu ? 1 : 0, h->d_status, jv.nw * jv.waves, waves, p.gn, p.gm, p.tmask,
+                             c.s, p.tile_m, direct ? K : 0, lastadj, p.xtouch, p.tnear) != 0)
         return fail(TSG_ERR_HIP, std::string("tcsc launch: ") + hipGetErrorString(hipGetLastError()));
     rc = timing_end(h, slot, c.s);
     if (rc || direct) return rc;
     return work_end(h, c);
 }
 
-int run_dev(tsg_tcsc *h, const float *dX, const float *db, const float *dalpha, float *dY, int M,
+int run_dev(tsg_tcsc *h, const float *dX, const float *db, const float *dalpha, float *dY, int64_t ldY, int M,
             int N, int K, hipStream_t s, bool prelu)
 {
     if (!h) return fail(TSG_ERR_ARG, "null handle");
@@ -533,6 +534,8 @@ int run_dev(tsg_tcsc *h, const float *dX, const float *db, const float *dalpha, 
                                      std::to_string(h->plan.N) + ", call has K=" + std::to_string(K) +
                                      " N=" + std::to_string(N));
     if (M < 0) return fail(TSG_ERR_ARG, "M < 0");
+    if (ldY < N)  // rows would overlap: refused before anything is enqueued
+        return fail(TSG_ERR_ARG, "ldY=" + std::to_string(ldY) + " is less than N=" + std::to_string(N));
     if (M == 0 || N == 0) return TSG_OK;
     if (!dY || !db || (K > 0 && !dX) || (prelu && !dalpha))
         return fail(TSG_ERR_ARG, "null device pointer");
@@ -542,7 +545,7 @@ int run_dev(tsg_tcsc *h, const float *dX, const float *db, const float *dalpha, 
     std::lock_guard<std::mutex> lk(h->mu);
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     HIP_TRY(hipStreamIsCapturing(s, &cap));
-    const Call c{dX, db, dalpha, dY, M, s, prelu, cap != hipStreamCaptureStatusNone};
+    const Call c{dX, db, dalpha, dY, ldY, M, s, prelu, cap != hipStreamCaptureStatusNone};
     CallPlan p = tsg::plan_call(h->plan, M);
     if (p.is_ell()) return run_ell(h, p, c);
     if (!p.is_jit()) return run_rx(h, p, c);
@@ -596,7 +599,8 @@ int run_host_impl(tsg_tcsc *h, const float *X, const float *b, const float *alph
                   bool prelu)
 {
     if (!h) return fail(TSG_ERR_ARG, "null handle");
-    if (N != h->plan.N || K != h->plan.K) return run_dev(h, nullptr, nullptr, nullptr, nullptr, M, N, K, nullptr, prelu);
+    if (N != h->plan.N || K != h->plan.K)
+        return run_dev(h, nullptr, nullptr, nullptr, nullptr, N, M, N, K, nullptr, prelu);
     if (M < 0) return fail(TSG_ERR_ARG, "M < 0");
     if (M == 0 || N == 0) return TSG_OK;
     if (!Y || !b || (K > 0 && !X) || (prelu && !alpha)) return fail(TSG_ERR_ARG, "null host pointer");
@@ -627,7 +631,7 @@ int run_host_impl(tsg_tcsc *h, const float *X, const float *b, const float *alph
     const int rows = tsg::host_chunk_rows(h->plan, h->host_chunks, M);
     if (rows >= M) {
         if (xb) HIP_TRY(hipMemcpyAsync(h->d_x, X, xb, hipMemcpyHostToDevice, s));
-        rc = run_dev(h, h->d_x, h->d_b, h->d_alpha, h->d_y, M, N, K, s, prelu);
+        rc = run_dev(h, h->d_x, h->d_b, h->d_alpha, h->d_y, N, M, N, K, s, prelu);
         if (rc) return rc;
         HIP_TRY(hipMemcpyAsync(Y, h->d_y, yb, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
@@ -695,7 +699,7 @@ int run_host_impl(tsg_tcsc *h, const float *X, const float *b, const float *alph
         if (e == hipSuccess) e = hipEventRecord(h->ev_in[i], h->s_in);
         if (e == hipSuccess) e = hipStreamWaitEvent(s, h->ev_in[i], 0);
         if (e != hipSuccess) return stop(fail(TSG_ERR_HIP, std::string("host pipeline (X chunk): ") + hipGetErrorString(e)));
-        rc = run_dev(h, h->d_x + r0 * K, h->d_b, h->d_alpha, h->d_y + r0 * N, (int)nr, N, K, s, prelu);
+        rc = run_dev(h, h->d_x + r0 * K, h->d_b, h->d_alpha, h->d_y + r0 * N, N, (int)nr, N, K, s, prelu);
         if (rc) return stop(rc);
         e = hipEventRecord(h->ev_c[i], s);
         if (e != hipSuccess) return stop(fail(TSG_ERR_HIP, std::string("host pipeline (event): ") + hipGetErrorString(e)));
@@ -1242,14 +1246,26 @@ extern "C" int tcsc_hip_gemm_prelu(tsg_tcsc *h, const float *X, const float *b, 
 extern "C" int tcsc_hip_gemm_dev(tsg_tcsc *h, const float *dX, const float *db, float *dY, int M,
                                  int N, int K, void *stream)
 {
-    return run_dev(h, dX, db, nullptr, dY, M, N, K, (hipStream_t)stream, false);
+    return run_dev(h, dX, db, nullptr, dY, N, M, N, K, (hipStream_t)stream, false);
 }
 
 extern "C" int tcsc_hip_gemm_prelu_dev(tsg_tcsc *h, const float *dX, const float *db,
                                        const float *dalpha, float *dY, int M, int N, int K,
                                        void *stream)
 {
-    return run_dev(h, dX, db, dalpha, dY, M, N, K, (hipStream_t)stream, true);
+    return run_dev(h, dX, db, dalpha, dY, N, M, N, K, (hipStream_t)stream, true);
+}
+
+extern "C" int tcsc_hip_gemm_dev_ld(tsg_tcsc *h, const float *dX, const float *db, float *dY, int64_t ldY,
+                                    int M, int N, int K, void *stream)
+{
+    return run_dev(h, dX, db, nullptr, dY, ldY, M, N, K, (hipStream_t)stream, false);
+}
+
+extern "C" int tcsc_hip_gemm_prelu_dev_ld(tsg_tcsc *h, const float *dX, const float *db, const float *dalpha,
+                                          float *dY, int64_t ldY, int M, int N, int K, void *stream)
+{
+    return run_dev(h, dX, db, dalpha, dY, ldY, M, N, K, (hipStream_t)stream, true);
 }
 
 extern "C" int tcsc_hip_info(const tsg_tcsc *h, tsg_info *o)

@@ -237,8 +237,8 @@ __device__ __forceinline__ void ell_stage(float *xs, const float *__restrict__ X
 template <int LG, int RPL, int WPG, int LA, bool PRELU>
 __global__ __launch_bounds__(WPG * 64) void tsg_tcsc_ell_kernel(
     const float *__restrict__ X, const uint4 *__restrict__ ent, const uint2 *__restrict__ tab,
-    const float *__restrict__ b, const float *__restrict__ alpha, float *__restrict__ Y, int M, int N, int K,
-    int C, int nch, int steps, int nsg, int xb, int zr)
+    const float *__restrict__ b, const float *__restrict__ alpha, float *__restrict__ Y, int64_t ldY, int M, int N,
+    int K, int C, int nch, int steps, int nsg, int xb, int zr)
 {
     constexpr int MT = LG * RPL;                     // M rows of the tile
     constexpr int CPW = 64 / LG;                     // columns per wave
@@ -305,7 +305,7 @@ __global__ __launch_bounds__(WPG * 64) void tsg_tcsc_ell_kernel(
         if (m >= M) break;
         float v = y[r] + bn;                         // comp.h:63
         if (PRELU) v = (v > 0) ? v : an * v;         // comp_prelu.h:57-67
-        Y[(size_t)m * N + n] = v;
+        Y[(size_t)m * (size_t)ldY + n] = v;
     }
 }
 
@@ -351,8 +351,8 @@ struct PcShape {
 template <int MT, int E, bool PRELU>
 __global__ __launch_bounds__(64 * (MT + E / 8)) void tsg_tcsc_ell_pc_kernel(
     const float *__restrict__ X, const uint4 *__restrict__ ent, const uint2 *__restrict__ tab,
-    const float *__restrict__ b, const float *__restrict__ alpha, float *__restrict__ Y, int M, int N, int K,
-    int C, int nsg)
+    const float *__restrict__ b, const float *__restrict__ alpha, float *__restrict__ Y, int64_t ldY, int M, int N,
+    int K, int C, int nsg)
 {
     using S = PcShape<MT, E>;
     static_assert(S::NT == 64 * (MT + E / 8), "launch bounds");
@@ -433,7 +433,7 @@ __global__ __launch_bounds__(64 * (MT + E / 8)) void tsg_tcsc_ell_pc_kernel(
         if (n >= N || m0 + r >= M) return;
         float v = y + b[n];                          // comp.h:63
         if (PRELU) v = (v > 0) ? v : alpha[n] * v;   // comp_prelu.h:57-67
-        Y[(size_t)(m0 + r) * N + n] = v;
+        Y[(size_t)(m0 + r) * (size_t)ldY + n] = v;
     } else {
         const uint32_t base = (uint32_t)(uintptr_t)(lds_f *)xs;
         // A block's 8 entries, all MT rows each (one LDS read per entry), are
@@ -530,7 +530,7 @@ namespace {
 
 template <int LG, int RPL, int WPG, int LA>
 int launch_ell_la(const float *X, const uint4 *ent, const uint2 *tab, const float *b, const float *alpha, float *Y,
-                  int M, int N, int K, int C, int nch, int xb, int zr, int prelu, hipStream_t s)
+                  int64_t ldY, int M, int N, int K, int C, int nch, int xb, int zr, int prelu, hipStream_t s)
 {
     constexpr int MT = LG * RPL, CPW = 64 / LG;
     const int nsg = (N + WPG * CPW - 1) / (WPG * CPW);
@@ -540,10 +540,10 @@ int launch_ell_la(const float *X, const uint4 *ent, const uint2 *tab, const floa
     const dim3 grid((unsigned)(nsg * mtiles)), block(WPG * 64);
     if (prelu)
         hipLaunchKernelGGL((tsg_tcsc_ell_kernel<LG, RPL, WPG, LA, true>), grid, block, lds, s, X, ent, tab, b, alpha,
-                           Y, M, N, K, C, nch, steps, nsg, xb, zr);
+                           Y, ldY, M, N, K, C, nch, steps, nsg, xb, zr);
     else
         hipLaunchKernelGGL((tsg_tcsc_ell_kernel<LG, RPL, WPG, LA, false>), grid, block, lds, s, X, ent, tab, b, alpha,
-                           Y, M, N, K, C, nch, steps, nsg, xb, zr);
+                           Y, ldY, M, N, K, C, nch, steps, nsg, xb, zr);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -560,11 +560,11 @@ int pick_la()
 
 template <int LG, int RPL, int WPG>
 int launch_ell_t(const float *X, const uint4 *ent, const uint2 *tab, const float *b, const float *alpha, float *Y,
-                 int M, int N, int K, int C, int nch, int xb, int zr, int prelu, hipStream_t s)
+                 int64_t ldY, int M, int N, int K, int C, int nch, int xb, int zr, int prelu, hipStream_t s)
 {
     if (pick_la() == 2)
-        return launch_ell_la<LG, RPL, WPG, 2>(X, ent, tab, b, alpha, Y, M, N, K, C, nch, xb, zr, prelu, s);
-    return launch_ell_la<LG, RPL, WPG, 1>(X, ent, tab, b, alpha, Y, M, N, K, C, nch, xb, zr, prelu, s);
+        return launch_ell_la<LG, RPL, WPG, 2>(X, ent, tab, b, alpha, Y, ldY, M, N, K, C, nch, xb, zr, prelu, s);
+    return launch_ell_la<LG, RPL, WPG, 1>(X, ent, tab, b, alpha, Y, ldY, M, N, K, C, nch, xb, zr, prelu, s);
 }
 
 }  // namespace
@@ -585,8 +585,8 @@ namespace {
 constexpr int64_t kEllWideWgs = 224;  // 7/8 of the CUs
 
 template <int LG, int RPL>
-int launch_lg(const float *X, const uint4 *e, const uint2 *t, const float *b, const float *alpha, float *Y, int M,
-              int N, int K, int C, int nch, int xb, int zr, int prelu, hipStream_t s)
+int launch_lg(const float *X, const uint4 *e, const uint2 *t, const float *b, const float *alpha, float *Y,
+              int64_t ldY, int M, int N, int K, int C, int nch, int xb, int zr, int prelu, hipStream_t s)
 {
     constexpr int MT = LG * RPL, CPW = 64 / LG;
     const int64_t waves = (int64_t)((N + CPW - 1) / CPW) * ((M + MT - 1) / MT);
@@ -595,24 +595,26 @@ int launch_lg(const float *X, const uint4 *e, const uint2 *t, const float *b, co
         const char *v = knob_value("TSG_ELL_WPG");
         return v ? atoi(v) : 0;
     }();
-    if (env_wpg == 4) return launch_ell_t<LG, RPL, 4>(X, e, t, b, alpha, Y, M, N, K, C, nch, xb, zr, prelu, s);
+    if (env_wpg == 4) return launch_ell_t<LG, RPL, 4>(X, e, t, b, alpha, Y, ldY, M, N, K, C, nch, xb, zr, prelu, s);
     if constexpr (RPL <= 2) {
-        if (env_wpg == 8) return launch_ell_t<LG, RPL, 8>(X, e, t, b, alpha, Y, M, N, K, C, nch, xb, zr, prelu, s);
-        if (env_wpg == 16) return launch_ell_t<LG, RPL, 16>(X, e, t, b, alpha, Y, M, N, K, C, nch, xb, zr, prelu, s);
+        if (env_wpg == 8) return launch_ell_t<LG, RPL, 8>(X, e, t, b, alpha, Y, ldY, M, N, K, C, nch, xb, zr, prelu, s);
+        if (env_wpg == 16)
+            return launch_ell_t<LG, RPL, 16>(X, e, t, b, alpha, Y, ldY, M, N, K, C, nch, xb, zr, prelu, s);
     }
     if constexpr (RPL <= 2) {
         auto one_round = [&](int64_t wpg) {  // >= 7/8 of the CUs busy, no second round
             const int64_t wgs = (waves + wpg - 1) / wpg;
             return wgs >= kEllWideWgs && wgs <= 256 * per_cu;
         };
-        if (one_round(16)) return launch_ell_t<LG, RPL, 16>(X, e, t, b, alpha, Y, M, N, K, C, nch, xb, zr, prelu, s);
-        if (one_round(8)) return launch_ell_t<LG, RPL, 8>(X, e, t, b, alpha, Y, M, N, K, C, nch, xb, zr, prelu, s);
+        if (one_round(16))
+            return launch_ell_t<LG, RPL, 16>(X, e, t, b, alpha, Y, ldY, M, N, K, C, nch, xb, zr, prelu, s);
+        if (one_round(8)) return launch_ell_t<LG, RPL, 8>(X, e, t, b, alpha, Y, ldY, M, N, K, C, nch, xb, zr, prelu, s);
         if (waves > 256 * per_cu * 8)
-            return launch_ell_t<LG, RPL, 16>(X, e, t, b, alpha, Y, M, N, K, C, nch, xb, zr, prelu, s);
+            return launch_ell_t<LG, RPL, 16>(X, e, t, b, alpha, Y, ldY, M, N, K, C, nch, xb, zr, prelu, s);
         if (waves > 256 * per_cu * 4)
-            return launch_ell_t<LG, RPL, 8>(X, e, t, b, alpha, Y, M, N, K, C, nch, xb, zr, prelu, s);
+            return launch_ell_t<LG, RPL, 8>(X, e, t, b, alpha, Y, ldY, M, N, K, C, nch, xb, zr, prelu, s);
     }
-    return launch_ell_t<LG, RPL, 4>(X, e, t, b, alpha, Y, M, N, K, C, nch, xb, zr, prelu, s);
+    return launch_ell_t<LG, RPL, 4>(X, e, t, b, alpha, Y, ldY, M, N, K, C, nch, xb, zr, prelu, s);
 }
 
 // lanes per column of an M tile: the default, or TSG_ELL_LG (diagnostic sweeps)
@@ -633,7 +635,7 @@ constexpr size_t pc_lds(int C)
 
 template <int MT, int E>
 int launch_pc_t(const float *X, const uint4 *ent, const uint2 *tab, const float *b, const float *alpha, float *Y,
-                int M, int N, int K, int C, int prelu, hipStream_t s)
+                int64_t ldY, int M, int N, int K, int C, int prelu, hipStream_t s)
 {
     using S = PcShape<MT, E>;
     const int nsg = (N + 63) / 64;
@@ -641,11 +643,11 @@ int launch_pc_t(const float *X, const uint4 *ent, const uint2 *tab, const float 
     const size_t lds = pc_lds<MT, E>(C);
     const dim3 grid((unsigned)(nsg * mtiles)), block(S::NT);
     if (prelu)
-        hipLaunchKernelGGL((tsg_tcsc_ell_pc_kernel<MT, E, true>), grid, block, lds, s, X, ent, tab, b, alpha, Y, M, N,
-                           K, C, nsg);
+        hipLaunchKernelGGL((tsg_tcsc_ell_pc_kernel<MT, E, true>), grid, block, lds, s, X, ent, tab, b, alpha, Y, ldY, M,
+                           N, K, C, nsg);
     else
-        hipLaunchKernelGGL((tsg_tcsc_ell_pc_kernel<MT, E, false>), grid, block, lds, s, X, ent, tab, b, alpha, Y, M, N,
-                           K, C, nsg);
+        hipLaunchKernelGGL((tsg_tcsc_ell_pc_kernel<MT, E, false>), grid, block, lds, s, X, ent, tab, b, alpha, Y, ldY,
+                           M, N, K, C, nsg);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -688,7 +690,8 @@ size_t ell_pc_lds_bytes(int variant, int C)
 }
 
 int launch_tcsc_ell_pc(int variant, const float *X, const uint32_t *ent, const uint32_t *tab, const float *b,
-                       const float *alpha, float *Y, int M, int N, int K, int C, int nch, int prelu, void *stream)
+                       const float *alpha, float *Y, int64_t ldY, int M, int N, int K, int C, int nch, int prelu,
+                       void *stream)
 {
     // one stream per column, X chunk + ring within a workgroup's LDS
     if (nch != 1 || ell_pc_lds_bytes(variant, C) == 0 || ell_pc_lds_bytes(variant, C) > kLdsBytes) return -2;
@@ -696,15 +699,15 @@ int launch_tcsc_ell_pc(int variant, const float *X, const uint32_t *ent, const u
     const uint4 *e = reinterpret_cast<const uint4 *>(ent);
     const uint2 *t = reinterpret_cast<const uint2 *>(tab);
     switch (pc_phase(M, N, C)) {
-    case 16: return launch_pc_t<1, 16>(X, e, t, b, alpha, Y, M, N, K, C, prelu, s);
-    case 64: return launch_pc_t<1, 64>(X, e, t, b, alpha, Y, M, N, K, C, prelu, s);
-    default: return launch_pc_t<1, 32>(X, e, t, b, alpha, Y, M, N, K, C, prelu, s);  // 1 consumer + 4 producer waves
+    case 16: return launch_pc_t<1, 16>(X, e, t, b, alpha, Y, ldY, M, N, K, C, prelu, s);
+    case 64: return launch_pc_t<1, 64>(X, e, t, b, alpha, Y, ldY, M, N, K, C, prelu, s);
+    default: return launch_pc_t<1, 32>(X, e, t, b, alpha, Y, ldY, M, N, K, C, prelu, s);  // 1 consumer, 4 producers
     }
 }
 
 int launch_tcsc_ell(int variant, const float *X, const uint32_t *ent, const uint32_t *tab, const float *b,
-                    const float *alpha, float *Y, int M, int N, int K, int C, int nch, int xb, int zr, int prelu,
-                    void *stream)
+                    const float *alpha, float *Y, int64_t ldY, int M, int N, int K, int C, int nch, int xb, int zr,
+                    int prelu, void *stream)
 {
     // the second X^T copy and the bank-window schedule serve the 8-row tile's
     // 4-lane columns only (tsg_host.cpp build_ell_image)
@@ -713,9 +716,9 @@ int launch_tcsc_ell(int variant, const float *X, const uint32_t *ent, const uint
     const uint4 *e = reinterpret_cast<const uint4 *>(ent);
     const uint2 *t = reinterpret_cast<const uint2 *>(tab);
 #define TSG_ELL_LG(lg, rpl) \
-    case lg: return launch_lg<lg, rpl>(X, e, t, b, alpha, Y, M, N, K, C, nch, xb, zr, prelu, s)
+    case lg: return launch_lg<lg, rpl>(X, e, t, b, alpha, Y, ldY, M, N, K, C, nch, xb, zr, prelu, s)
     switch (variant) {
-    case 0: return launch_ell_t<1, 1, 1>(X, e, t, b, alpha, Y, M, N, K, C, nch, xb, zr, prelu, s);  // MT = 1
+    case 0: return launch_ell_t<1, 1, 1>(X, e, t, b, alpha, Y, ldY, M, N, K, C, nch, xb, zr, prelu, s);  // MT = 1
     case 1:                                                                                   // MT = 4
         switch (pick_lg(4)) {
             TSG_ELL_LG(4, 1);

@@ -216,12 +216,13 @@ struct JitModule {
                      bool rows64 = false, bool half = false, bool pair = false);  // "" on success
     void unload();
 };
+// ldY: floats from one Y row to the next (>= N; every kernel below takes it);
 // xrow > 0: the 64-row image stages straight from X (xrow floats per row);
 // lastadj: bytes the row layout's last chunk starts below its slot (direct X);
 // xtouch: the per-group code touches (v[lane128 + 1]) spread over the lines;
 // tnear: the code touches' window starts at the step's own position
 int launch_tcsc_jit(const JitModule &jm, const float *XT, int Mp, const uint32_t *wcode,
-                    const float *b, const float *alpha, float *Y, int M, int N, int Npad, int nch,
+                    const float *b, const float *alpha, float *Y, int64_t ldY, int M, int N, int Npad, int nch,
                     int prelu, uint32_t *status, int tile_cols, int waves, int gn, int gm, int tmask,
                     void *stream, int tile_m = kJitTileM, int xrow = 0, int lastadj = 0, int xtouch = 0,
                     int tnear = 0);
@@ -269,15 +270,16 @@ constexpr int kEllSchedZeroRows = 8;
 void build_ell_image(const int32_t *csp, const int32_t *csn, const int32_t *rip, const int32_t *rin, int K, int N,
                      int Cmax, int MT, EllImage &img, int copies = 1, bool sched = false);
 int launch_tcsc_ell(int variant, const float *X, const uint32_t *ent, const uint32_t *tab, const float *b,
-                    const float *alpha, float *Y, int M, int N, int K, int C, int nch, int xb, int zr, int prelu,
-                    void *stream);
+                    const float *alpha, float *Y, int64_t ldY, int M, int N, int K, int C, int nch, int xb, int zr,
+                    int prelu, void *stream);
 // the producer/consumer walk (tsg_tcsc_ell_pc_kernel) of variant 0 (M = 1) when
 // K fits one chunk and the chunk plus its LDS ring fit kLdsBytes
 // (ell_pc_lds_bytes; 0 = no such variant); -2 = not available for this image
 constexpr size_t kLdsBytes = 160 * 1024;
 size_t ell_pc_lds_bytes(int variant, int C);
 int launch_tcsc_ell_pc(int variant, const float *X, const uint32_t *ent, const uint32_t *tab, const float *b,
-                       const float *alpha, float *Y, int M, int N, int K, int C, int nch, int prelu, void *stream);
+                       const float *alpha, float *Y, int64_t ldY, int M, int N, int K, int C, int nch, int prelu,
+                       void *stream);
 
 // Environment knobs (csrc/tsg_knobs.cpp): A/B studies and tests, none of
 // which changes a result.  knob_check: "" when every set knob has an
@@ -311,7 +313,7 @@ int launch_transpose_pairs(const float *X, float *XP, int M, int K, int Mp, int 
 int launch_transpose_quads(const float *X, float *XQ, int M, int K, int Mp, int Kp, int piece_rows, void *stream,
                            int chunk = kJit64Chunk);
 int launch_tcsc_rx(const float *XT, int Mp, const uint32_t *wstart, const uint32_t *ent,
-                   const float *b, const float *alpha, float *Y, int M, int N, int Npad, int nch,
+                   const float *b, const float *alpha, float *Y, int64_t ldY, int M, int N, int Npad, int nch,
                    int prelu, void *stream);
 
 }  // namespace tsg

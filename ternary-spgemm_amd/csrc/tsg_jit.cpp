@@ -930,6 +930,9 @@ void build_jit_code(const int32_t *csp, const int32_t *csn, const int32_t *rip, 
 // ------------------------------------------------------------ code object --
 namespace {
 
+// Marker kernel of a dispatcher whose argument list ends in ldY (tsg_jit_kernel.hip)
+constexpr const char *kJitArgsMarker = "tsg_jit_args_ldy";
+
 // The dispatcher of a stream width: tsg_jit.co (kJitNW columns per wave) or
 // tsg_jit_w<nw>.co (same kernel built with TSG_JIT_NW=nw, Makefile); 4-wave
 // workgroups: tsg_jit_w<nw>_4w.co (TSG_JIT_WAVES=4); the 64-row image:
@@ -1059,6 +1062,16 @@ std::string JitModule::load(const std::vector<uint32_t> &code, int nw, int waves
         (void)hipModuleUnload(m);
         return std::string("hipModuleGetFunction: ") + hipGetErrorString(e);
     }
+    // the argument list launch_tcsc_jit passes ends in ldY: a template built
+    // before that (a TSG_JIT_DIR override) lacks this marker kernel and is
+    // refused like a missing one, never launched with the wrong arguments
+    hipFunction_t mark = nullptr;
+    if (hipModuleGetFunction(&mark, m, kJitArgsMarker) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipModuleUnload(m);
+        return std::string("jit template ") + template_name(nw, waves, r64, half, pair) +
+               " predates the dispatcher's ldY argument (no " + kJitArgsMarker + "); rebuild it";
+    }
     module = m;
     function = fn;
     probe = pf;
@@ -1082,7 +1095,7 @@ int launch_jit_probe(const JitModule &jm, uint32_t *status, void *stream)
 }
 
 int launch_tcsc_jit(const JitModule &jm, const float *XT, int Mp, const uint32_t *wcode, const float *b,
-                    const float *alpha, float *Y, int M, int N, int Npad, int nch, int prelu,
+                    const float *alpha, float *Y, int64_t ldY, int M, int N, int Npad, int nch, int prelu,
                     uint32_t *status, int tile_cols, int waves, int gn, int gm, int tmask, void *stream,
                     int tile_m, int xrow, int lastadj, int xtouch, int tnear)
 {
@@ -1090,7 +1103,7 @@ int launch_tcsc_jit(const JitModule &jm, const float *XT, int Mp, const uint32_t
     void *params[] = {(void *)&XT, (void *)&Mp, (void *)&wcode, (void *)&b, (void *)&alpha, (void *)&Y,
                       (void *)&M, (void *)&N, (void *)&nch, (void *)&mtiles, (void *)&ntiles, (void *)&prelu,
                       (void *)&status, (void *)&gn, (void *)&gm, (void *)&tmask, (void *)&xrow, (void *)&lastadj,
-                      (void *)&xtouch, (void *)&tnear};
+                      (void *)&xtouch, (void *)&tnear, (void *)&ldY};
     hipError_t e = hipModuleLaunchKernel((hipFunction_t)jm.function, (unsigned)(mtiles * ntiles), 1, 1,
                                          (unsigned)waves * 64u, 1, 1, 0, (hipStream_t)stream, params, nullptr);
     return e == hipSuccess ? 0 : -1;

@@ -170,12 +170,17 @@ extern "C" __global__ __launch_bounds__(64) void tsg_jit_probe(uint32_t *__restr
     }
 }
 
+// Marker (tsg_jit.cpp JitModule::load looks it up, nothing launches it): this
+// code object's dispatcher takes the argument list that ends in ldY.  A
+// template without it is refused at load.
+extern "C" __global__ __launch_bounds__(64) void tsg_jit_args_ldy() {}
+
 // (the half ring: two workgroups per CU, so at most 256 VGPRs -- two waves per SIMD)
 extern "C" __global__ __launch_bounds__(kJThreads, kJHalf ? 2 : 1) void TSG_JIT_KERNEL_NAME(
     const float *__restrict__ XT, int Mp, const uint32_t *__restrict__ wcode,
     const float *__restrict__ b, const float *__restrict__ alpha, float *__restrict__ Y, int M, int N,
     int nch, int mtiles, int ntiles, int prelu, uint32_t *__restrict__ status, int gn, int gm,
-    int tmask, int xrow, int lastadj, int xtouch, int tnear)
+    int tmask, int xrow, int lastadj, int xtouch, int tnear, int64_t ldY)
 {
     __shared__ __attribute__((aligned(16))) char lds[kJRing * kJBufBytes];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -389,7 +394,7 @@ extern "C" __global__ __launch_bounds__(kJThreads, kJHalf ? 2 : 1) void TSG_JIT_
     for (int r = 0; r < kJRowsPerLane; r++) {
         const int m = m0 + kJRowsPerLane * lane + r;
         if (m >= M) continue;
-        float *yrow = Y + (size_t)m * N + ncol0;
+        float *yrow = Y + (size_t)m * (size_t)ldY + ncol0;  // ldY >= N floats per Y row
         float v[kJNW];
 #pragma unroll
         for (int c = 0; c < kJNW; c++) {

@@ -109,6 +109,22 @@ class ShardedTCSC:
             b = b.contiguous()
         return self.local.gemm_torch(X, b, Y_local)
 
+    def forward_into(self, X, b_full, Y_full):
+        """X [M, K] -> this rank's block written straight into Y_full[:, n0:n1]
+        (Y_full [M, N] row-major on this rank's GPU; the kernel's output row
+        stride is N, tcsc_hip_gemm_dev_ld); returns that view.  No scratch
+        block, no reorder: shards of one process (a loop over ShardedTCSC
+        objects on one GPU) fill one Y_full.  The multi-rank gather still goes
+        through forward + GatherPipeline (all_gather_into_tensor needs a
+        contiguous input)."""
+        if Y_full.dim() != 2 or tuple(Y_full.shape) != (X.shape[0], self.N) or not Y_full.is_contiguous():
+            raise T.TSGError(1, "forward_into", f"Y_full must be a row-major [{X.shape[0]}, {self.N}] tensor, got "
+                                                f"{list(Y_full.shape)} with strides {Y_full.stride()}")
+        b = b_full[self.n0:self.n1]
+        if not b.is_contiguous():
+            b = b.contiguous()
+        return self.local.gemm_torch_into(X, b, Y_full[:, self.n0:self.n1])
+
 
 def allgather_columns(Y_local, N: int, world: int, group=None):
     """All-gather the Y column blocks of every rank into row-major [M, N].

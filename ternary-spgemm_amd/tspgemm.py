@@ -48,6 +48,7 @@ EXPORTED_SYMBOLS = (
     "tcsc_hip_host_register", "tcsc_hip_host_unregister", "tcsc_hip_set_far", "tcsc_hip_call_far",
     "tsg_jit_codegen_far", "tsg_call_plan", "tsg_call_xtouch", "tsg_knob_check", "tcsc_hip_set_tile_rows", "tcsc_hip_call_tile_rows",
     "tsg_jit_codegen64", "tsg_jit_codegen64h", "tcsc_hip_call_launches",
+    "tcsc_hip_gemm_dev_ld", "tcsc_hip_gemm_prelu_dev_ld",
 )
 
 
@@ -98,6 +99,8 @@ def lib() -> C.CDLL:
     L.tcsc_hip_gemm_dev.argtypes = [H, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]
     L.tcsc_hip_gemm_prelu.argtypes = [H, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int]
     L.tcsc_hip_gemm_prelu_dev.argtypes = [H, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]
+    L.tcsc_hip_gemm_dev_ld.argtypes = [H, vp, vp, vp, C.c_int64, C.c_int, C.c_int, C.c_int, vp]
+    L.tcsc_hip_gemm_prelu_dev_ld.argtypes = [H, vp, vp, vp, vp, C.c_int64, C.c_int, C.c_int, C.c_int, vp]
     L.tcsc_hip_reserve.argtypes = [H, C.c_int]
     L.tcsc_hip_info.argtypes = [H, C.POINTER(tsg_info)]
     L.tcsc_hip_to_dense.argtypes = [H, vp, C.c_int, C.c_int]
@@ -592,8 +595,17 @@ class TCSCDevice:
 
     # ---- device pointers (torch tensors), asynchronous on `stream` ----
     def gemm_dev(self, dX: int, db: int, dY: int, M: int, stream: int = 0,
-                 dalpha: Optional[int] = None) -> None:
-        if dalpha is None:
+                 dalpha: Optional[int] = None, ldY: Optional[int] = None) -> None:
+        """ldY (floats, >= N): row m of the result starts at dY + m * ldY
+        (tcsc_hip_gemm_dev_ld); None = the dense [M, N] block."""
+        if ldY is not None:
+            if dalpha is None:
+                _check(lib().tcsc_hip_gemm_dev_ld(self._h, dX, db, dY, int(ldY), M, self.N, self.K,
+                                                  stream or None), "tcsc_hip_gemm_dev_ld")
+            else:
+                _check(lib().tcsc_hip_gemm_prelu_dev_ld(self._h, dX, db, dalpha, dY, int(ldY), M, self.N, self.K,
+                                                        stream or None), "tcsc_hip_gemm_prelu_dev_ld")
+        elif dalpha is None:
             _check(lib().tcsc_hip_gemm_dev(self._h, dX, db, dY, M, self.N, self.K, stream or None),
                    "tcsc_hip_gemm_dev")
         else:
@@ -624,6 +636,40 @@ class TCSCDevice:
         stream = torch.cuda.current_stream(dev).cuda_stream
         self.gemm_dev(X.data_ptr(), b.data_ptr(), Y.data_ptr(), M, stream,
                       None if alpha is None else alpha.data_ptr())
+        return Y
+
+    def gemm_torch_into(self, X, b, Y, alpha=None):
+        """gemm_torch into a strided output: Y is a float32 [M, N] tensor on the
+        handle's device whose rows are contiguous (Y.stride(1) == 1) and do not
+        overlap (Y.stride(0) >= N; any row stride when M == 1) -- a column
+        slice of a wider row-major tensor.  Only Y's own floats are written;
+        returns Y.  X, b and alpha as in gemm_torch."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if not (isinstance(X, torch.Tensor) and X.dim() == 2 and X.shape[1] == self.K):
+            raise TSGError(1, "gemm_torch_into", f"X must be a [M, {self.K}] tensor, got "
+                                                 f"{tuple(X.shape) if isinstance(X, torch.Tensor) else type(X)}")
+        M = X.shape[0]
+        for name, t, shape in (("X", X, (M, self.K)), ("b", b, (self.N,)), ("alpha", alpha, (self.N,))):
+            if t is None:
+                continue
+            if t.dtype != torch.float32 or t.device != dev or not t.is_contiguous() or tuple(t.shape) != shape:
+                raise TSGError(1, "gemm_torch_into", f"{name} must be a contiguous float32 {list(shape)} tensor on "
+                                                     f"{dev}, got {t.dtype} {list(t.shape)} on {t.device}"
+                                                     f"{'' if t.is_contiguous() else ' (non-contiguous)'}")
+        if not isinstance(Y, torch.Tensor) or Y.dtype != torch.float32 or Y.device != dev or \
+                tuple(Y.shape) != (M, self.N):
+            got = (Y.dtype, list(Y.shape), Y.device) if isinstance(Y, torch.Tensor) else type(Y)
+            raise TSGError(1, "gemm_torch_into", f"Y must be a float32 [{M}, {self.N}] tensor on {dev}, got {got}")
+        if self.N > 1 and Y.stride(1) != 1:
+            raise TSGError(1, "gemm_torch_into", f"Y's rows must be contiguous (stride(1) == 1), got {Y.stride()}")
+        # one row has no next row: any row stride describes it
+        ldY = self.N if M <= 1 else Y.stride(0)
+        if ldY < self.N:
+            raise TSGError(1, "gemm_torch_into", f"Y's rows overlap: stride(0) = {ldY} < N = {self.N}")
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        self.gemm_dev(X.data_ptr(), b.data_ptr(), Y.data_ptr(), M, stream,
+                      None if alpha is None else alpha.data_ptr(), ldY=ldY)
         return Y
 
     def reserve(self, max_M: int) -> None:
