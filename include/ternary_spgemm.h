@@ -152,7 +152,19 @@ int tcsc_hip_gemm_prelu_dev(tsg_tcsc *h, const float *dX, const float *db, const
  * stored float by float, the others with 16-byte stores; the result is the
  * same bit for bit.  Everything else -- stream semantics, reserve and graph
  * capture, the kernel an M picks -- is as tcsc_hip_gemm_dev, which is the
- * ldY = N case of this call.  Extension: no reference counterpart. */
+ * ldY = N case of this call.  Extension: no reference counterpart.
+ *
+ * Inputs of every device-pointer call: dX, db and dalpha need only 4-byte
+ * alignment, so they may be slices of larger buffers.  A 16-byte aligned dX
+ * with K % 4 == 0 selects the vector staging passes and the direct-X path of
+ * the 64-row image (one launch); any other dX takes the scalar passes and the
+ * staged copy -- the result is the same bit for bit.  No result depends on
+ * memory outside [dX, dX + M*K), [db, db + N) and [dalpha, dalpha + N), nor on
+ * a previous call on the handle (its X^T work buffer, its device copies of
+ * host operands, LDS); the inputs are never written.  Pinned by
+ * tests/test_gpu_isolation.py (operands inside NaN-filled buffers, an all-NaN
+ * call before the checked one): no value from outside those ranges reaches Y.
+ * That no address outside them is ever loaded is not claimed. */
 int tcsc_hip_gemm_dev_ld(tsg_tcsc *h, const float *dX, const float *db, float *dY, int64_t ldY,
                          int M, int N, int K, void *stream);
 int tcsc_hip_gemm_prelu_dev_ld(tsg_tcsc *h, const float *dX, const float *db, const float *dalpha,
