@@ -170,6 +170,41 @@ int tcsc_hip_gemm_dev_ld(tsg_tcsc *h, const float *dX, const float *db, float *d
 int tcsc_hip_gemm_prelu_dev_ld(tsg_tcsc *h, const float *dX, const float *db, const float *dalpha,
                                float *dY, int64_t ldY, int M, int N, int K, void *stream);
 
+/* The same two calls with X in a narrower element type: activations held in
+ * 16 or 8 bits go in as they are, without an fp32 copy of X.  dX is M x K
+ * row-major of the type xtype names, aligned to its element size only (it may
+ * be a slice of a larger buffer); b, alpha and Y stay fp32, and ldY, the
+ * stream semantics, tcsc_hip_reserve and graph capture are as on
+ * tcsc_hip_gemm_dev_ld.  The library widens X to fp32 inside the pass that
+ * reads it (its X^T staging pass, or the small-M walks' load of X), and
+ *
+ *   Y equals, bit for bit, what tcsc_hip_gemm_dev_ld gives on the element-wise
+ *   widened X.
+ *
+ * fp16 -> fp32, bf16 -> fp32 and int8 -> fp32 are exact: fp16 subnormals widen
+ * to their exact fp32 values, +-inf and -0 are kept, a NaN stays a NaN (its
+ * payload is not promised, as elsewhere in this library).  With int8 X every
+ * partial sum of a chain is an integer of magnitude at most 128 K, so the chains
+ * are integer-exact while K * 128 <= 2^24 (K * 127 < 2^24 without -128).
+ * TSG_X_F32 is tcsc_hip_gemm_dev_ld itself (the same path, direct X included).
+ * Any other xtype value returns TSG_ERR_ARG with a message and enqueues
+ * nothing.  A dX aligned to 4 elements with K % 4 == 0 selects the vector
+ * staging passes (one 8-byte load per four 16-bit elements, one 4-byte load
+ * per four int8), any other dX the scalar ones -- same result.  A 16- or
+ * 8-bit X is always staged (the weight-compiled images read fp32), so such a
+ * call uses the work buffer at every M that runs an image;
+ * tcsc_hip_reserve(h, max_M) sizes it for that.  The isolation paragraph above
+ * holds with [dX, dX + M*K) counted in elements of the type.  The kernel and
+ * image an M picks do not depend on the type.  Extension: no reference
+ * counterpart. */
+enum tsg_xtype { TSG_X_F32 = 0, TSG_X_F16 = 1, TSG_X_BF16 = 2, TSG_X_I8 = 3 };
+
+int tcsc_hip_gemm_dev_x(tsg_tcsc *h, const void *dX, int xtype, const float *db, float *dY,
+                        int64_t ldY, int M, int N, int K, void *stream);
+int tcsc_hip_gemm_prelu_dev_x(tsg_tcsc *h, const void *dX, int xtype, const float *db,
+                              const float *dalpha, float *dY, int64_t ldY, int M, int N, int K,
+                              void *stream);
+
 /* Pre-allocates the per-handle work buffer for row counts up to max_M and, on
  * the weight-compiled kernel, compiles every code image a call with M <= max_M
  * rows runs (and the small-M images), so no later such call allocates or

@@ -9,17 +9,27 @@
 //
 // tsg_transpose_kernel / tsg_transpose4_kernel (K % 4 == 0):
 //   X [M][K] -> X^T [Kp][Mp], zero padded.  HBM-bound copy (2 * 4 * M * K bytes).
+// Every staging pass is a template on X's element type T (float, xf16, xbf16,
+// xi8; tsg_xtype.h): it reads T through xload1 / xload4, which widen to fp32,
+// and writes the same fp32 layout whatever T is -- so the kernels that consume
+// the staged copy never see the type.  The vector forms read one quad (four
+// consecutive k of a row) per load: 16 B of fp32, 8 B of a 16-bit type, 4 B of
+// int8; they need X aligned to 4 elements and K % 4 == 0 (x_quad_aligned).
 // tsg_tcsc_rx_kernel: the register-X walk, the fallback when a W is too large
 //   for one weight-compiled image (> ~300 M nonzeros on one handle) or the
 //   generated image cannot be loaded (tsg_capi.cpp create_impl).
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "tsg_internal.h"
+#include "tsg_xtype.h"
 
 namespace tsg {
 
 // ------------------------------------------------------------------ kernel 1 --
-__global__ __launch_bounds__(256) void tsg_transpose_kernel(const float *__restrict__ X,
+template <typename T>
+__global__ __launch_bounds__(256) void tsg_transpose_kernel(const T *__restrict__ X,
                                                             float *__restrict__ XT, int M, int K,
                                                             int Mp, int Kp)
 {
@@ -29,7 +39,7 @@ __global__ __launch_bounds__(256) void tsg_transpose_kernel(const float *__restr
 #pragma unroll
     for (int i = 0; i < 16; i++) {
         const int m = m0 + ty + 4 * i, k = k0 + tx;
-        tile[ty + 4 * i][tx] = (m < M && k < K) ? X[(size_t)m * K + k] : 0.0f;
+        tile[ty + 4 * i][tx] = (m < M && k < K) ? xload1(X + (size_t)m * K + k) : 0.0f;
     }
     __syncthreads();
 #pragma unroll
@@ -39,10 +49,11 @@ __global__ __launch_bounds__(256) void tsg_transpose_kernel(const float *__restr
     }
 }
 
-// Same transpose with 16-byte accesses on both sides (K % 4 == 0 and X 16-byte
-// aligned): each lane loads 4 consecutive k of one m row and stores 4
+// Same transpose with a quad per load and 16-byte stores (K % 4 == 0 and X
+// aligned to 4 elements): each lane loads 4 consecutive k of one m row and stores 4
 // consecutive m of one X^T row -- a quarter of the memory instructions.
-__global__ __launch_bounds__(256) void tsg_transpose4_kernel(const float *__restrict__ X,
+template <typename T>
+__global__ __launch_bounds__(256) void tsg_transpose4_kernel(const T *__restrict__ X,
                                                              float *__restrict__ XT, int M, int K,
                                                              int Mp, int Kp)
 {
@@ -53,7 +64,7 @@ __global__ __launch_bounds__(256) void tsg_transpose4_kernel(const float *__rest
     for (int i = 0; i < 4; i++) {
         const int ml = r + 16 * i, m = m0 + ml, k = k0 + c4;
         float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        if (m < M && k < K) v = *reinterpret_cast<const float4 *>(X + (size_t)m * K + k);  // K % 4 == 0
+        if (m < M && k < K) v = xload4(X + (size_t)m * K + k);  // K % 4 == 0
         tile[ml][c4] = v.x;
         tile[ml][c4 + 1] = v.y;
         tile[ml][c4 + 2] = v.z;
@@ -73,11 +84,11 @@ __global__ __launch_bounds__(256) void tsg_transpose4_kernel(const float *__rest
 // pair p and M-row pair mp the 16 bytes at (p * Mp/2 + mp) * 16 hold
 // X[2mp][2p], X[2mp+1][2p], X[2mp][2p+1], X[2mp+1][2p+1]; zero outside M x K.
 // A 64 (m) x 64 (k) tile goes through LDS: loads along k (16 B per lane when
-// VEC: K % 4 == 0 and X 16-byte aligned), stores 16 B per lane, consecutive
+// VEC: K % 4 == 0 and X aligned to 4 elements), stores 16 B per lane, consecutive
 // lanes on consecutive mp (coalesced 512-B runs per pair row).  HBM-bound:
 // 8 * M * K bytes.
-template <bool VEC>
-__global__ __launch_bounds__(256) void tsg_transpose_pairs_kernel(const float *__restrict__ X,
+template <typename T, bool VEC>
+__global__ __launch_bounds__(256) void tsg_transpose_pairs_kernel(const T *__restrict__ X,
                                                                   float *__restrict__ XP, int M, int K,
                                                                   int Mp, int Kp)
 {
@@ -89,7 +100,7 @@ __global__ __launch_bounds__(256) void tsg_transpose_pairs_kernel(const float *_
         for (int i = 0; i < 4; i++) {
             const int ml = r + 16 * i, m = m0 + ml, k = k0 + c4;
             float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            if (m < M && k < K) v = *reinterpret_cast<const float4 *>(X + (size_t)m * K + k);  // K % 4 == 0
+            if (m < M && k < K) v = xload4(X + (size_t)m * K + k);  // K % 4 == 0
             tile[ml][c4] = v.x;
             tile[ml][c4 + 1] = v.y;
             tile[ml][c4 + 2] = v.z;
@@ -100,7 +111,7 @@ __global__ __launch_bounds__(256) void tsg_transpose_pairs_kernel(const float *_
 #pragma unroll
         for (int i = 0; i < 16; i++) {
             const int m = m0 + ty + 4 * i, k = k0 + tx;
-            tile[ty + 4 * i][tx] = (m < M && k < K) ? X[(size_t)m * K + k] : 0.0f;
+            tile[ty + 4 * i][tx] = (m < M && k < K) ? xload1(X + (size_t)m * K + k) : 0.0f;
         }
     }
     __syncthreads();
@@ -129,8 +140,8 @@ __global__ __launch_bounds__(256) void tsg_transpose_pairs_kernel(const float *_
 // 128-B line is the next piece's, copied by the neighbouring workgroup); no
 // LDS, no barrier.  A workgroup copies 4 consecutive pieces of one (chunk, M
 // tile).  HBM-bound: 8 * Mp * Kp bytes.
-template <bool VEC, int PR>
-__global__ __launch_bounds__(256) void tsg_transpose_quads_kernel(const float *__restrict__ X,
+template <typename T, bool VEC, int PR>
+__global__ __launch_bounds__(256) void tsg_transpose_quads_kernel(const T *__restrict__ X,
                                                                   float *__restrict__ XQ, int M, int K,
                                                                   int Mp, int Kp, int units)
 {
@@ -149,14 +160,14 @@ __global__ __launch_bounds__(256) void tsg_transpose_quads_kernel(const float *_
     const int k = 4 * (units * c + Q * qg + j / PR);
     float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     if (m < M) {
-        const float *row = X + (size_t)m * K;
+        const T *row = X + (size_t)m * K;
         if (VEC) {
-            if (k < K) v = *reinterpret_cast<const float4 *>(row + k);  // K % 4 == 0: whole quad inside
+            if (k < K) v = xload4(row + k);  // K % 4 == 0: whole quad inside
         } else {
-            if (k < K) v.x = row[k];
-            if (k + 1 < K) v.y = row[k + 1];
-            if (k + 2 < K) v.z = row[k + 2];
-            if (k + 3 < K) v.w = row[k + 3];
+            if (k < K) v.x = xload1(row + k);
+            if (k + 1 < K) v.y = xload1(row + k + 1);
+            if (k + 2 < K) v.z = xload1(row + k + 2);
+            if (k + 3 < K) v.w = xload1(row + k + 3);
         }
     }
     *reinterpret_cast<float4 *>(XQ + ((size_t)ct * units + pr) * 256 + (size_t)j * 4) = v;
@@ -170,8 +181,8 @@ __global__ __launch_bounds__(256) void tsg_transpose_quads_kernel(const float *_
 // of a row of X, so this is a gather-copy of row runs (no transpose): reads
 // and writes both run along rows.  Four workgroups per (chunk, M tile), 752
 // slots each.  HBM-bound: 2 * 4 * Mp * Kp bytes.
-template <bool VEC>
-__global__ __launch_bounds__(256) void tsg_transpose_rows_kernel(const float *__restrict__ X,
+template <typename T, bool VEC>
+__global__ __launch_bounds__(256) void tsg_transpose_rows_kernel(const T *__restrict__ X,
                                                                  float *__restrict__ XR, int M, int K, int Mp,
                                                                  int nch)
 {
@@ -188,14 +199,14 @@ __global__ __launch_bounds__(256) void tsg_transpose_rows_kernel(const float *__
         const int m = 64 * t + r, k = kb + 4 * q;
         float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         if (m < M) {
-            const float *row = X + (size_t)m * K;
+            const T *row = X + (size_t)m * K;
             if (VEC) {
-                if (k < K) v = *reinterpret_cast<const float4 *>(row + k);  // K % 4 == 0: whole quad inside
+                if (k < K) v = xload4(row + k);  // K % 4 == 0: whole quad inside
             } else {
-                if (k < K) v.x = row[k];
-                if (k + 1 < K) v.y = row[k + 1];
-                if (k + 2 < K) v.z = row[k + 2];
-                if (k + 3 < K) v.w = row[k + 3];
+                if (k < K) v.x = xload1(row + k);
+                if (k + 1 < K) v.y = xload1(row + k + 1);
+                if (k + 2 < K) v.z = xload1(row + k + 2);
+                if (k + 3 < K) v.w = xload1(row + k + 3);
             }
         }
         *reinterpret_cast<float4 *>(dst + (size_t)slot * 4) = v;
@@ -345,44 +356,55 @@ __global__ __launch_bounds__(kRxWaves * 64, 8 / kRxWaves) void tsg_tcsc_rx_kerne
 }
 
 // ---------------------------------------------------------------- launchers --
-int launch_transpose(const float *X, float *XT, int M, int K, int Mp, int Kp, void *stream)
+int launch_transpose(const void *X, int xtype, float *XT, int M, int K, int Mp, int Kp, void *stream)
 {
     dim3 grid((unsigned)((Kp + 63) / 64), (unsigned)(Mp / 64));
-    if (K % 4 == 0 && ((uintptr_t)X & 15) == 0)
-        hipLaunchKernelGGL(tsg_transpose4_kernel, grid, dim3(256), 0, (hipStream_t)stream, X, XT, M, K, Mp, Kp);
-    else
-        hipLaunchKernelGGL(tsg_transpose_kernel, grid, dim3(256), 0, (hipStream_t)stream, X, XT, M, K, Mp, Kp);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    const bool vec = K % 4 == 0 && x_quad_aligned(X, xtype);
+    return with_xtype(X, xtype, [&](auto *x) {
+        using T = std::remove_cv_t<std::remove_pointer_t<decltype(x)>>;
+        if (vec)
+            hipLaunchKernelGGL(tsg_transpose4_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, x, XT, M, K, Mp, Kp);
+        else
+            hipLaunchKernelGGL(tsg_transpose_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, x, XT, M, K, Mp, Kp);
+        return hipGetLastError() == hipSuccess ? 0 : -1;
+    });
 }
 
 
-int launch_transpose_pairs(const float *X, float *XP, int M, int K, int Mp, int Kp, void *stream)
+int launch_transpose_pairs(const void *X, int xtype, float *XP, int M, int K, int Mp, int Kp, void *stream)
 {
     // Mp is a multiple of 128 (the jit M tile) and Kp of 96: the 64 x 64 tiles
     // cover [0, Kp) x [0, Mp) exactly in m and up to 32 pad rows in k
     dim3 grid((unsigned)((Kp + 63) / 64), (unsigned)(Mp / 64));
-    if (K % 4 == 0 && ((uintptr_t)X & 15) == 0)
-        hipLaunchKernelGGL(tsg_transpose_pairs_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, X, XP, M, K,
-                           Mp, Kp);
-    else
-        hipLaunchKernelGGL(tsg_transpose_pairs_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, X, XP, M, K,
-                           Mp, Kp);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    const bool vec = K % 4 == 0 && x_quad_aligned(X, xtype);
+    return with_xtype(X, xtype, [&](auto *x) {
+        using T = std::remove_cv_t<std::remove_pointer_t<decltype(x)>>;
+        if (vec)
+            hipLaunchKernelGGL((tsg_transpose_pairs_kernel<T, true>), grid, dim3(256), 0, (hipStream_t)stream, x, XP, M,
+                               K, Mp, Kp);
+        else
+            hipLaunchKernelGGL((tsg_transpose_pairs_kernel<T, false>), grid, dim3(256), 0, (hipStream_t)stream, x, XP,
+                               M, K, Mp, Kp);
+        return hipGetLastError() == hipSuccess ? 0 : -1;
+    });
 }
 
-int launch_transpose_quads(const float *X, float *XQ, int M, int K, int Mp, int Kp, int piece_rows, void *stream,
-                           int chunk)
+int launch_transpose_quads(const void *X, int xtype, float *XQ, int M, int K, int Mp, int Kp, int piece_rows,
+                           void *stream, int chunk)
 {
     hipStream_t s = (hipStream_t)stream;
-    const bool vec = K % 4 == 0 && ((uintptr_t)X & 15) == 0;
+    const bool vec = K % 4 == 0 && x_quad_aligned(X, xtype);
     if (piece_rows == 0) {  // the row layout: 188-row chunks, 47 KiB per (chunk, M tile)
         if (chunk != 188 || Mp % 64 || Kp % 188) return -1;
         const int nch = Kp / 188;
         const int64_t blocks = (int64_t)nch * (Mp / 64) * 4;
         if (blocks >= ((int64_t)1 << 31)) return -1;
-        if (vec) hipLaunchKernelGGL(tsg_transpose_rows_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, X, XQ, M, K, Mp, nch);
-        else hipLaunchKernelGGL(tsg_transpose_rows_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, X, XQ, M, K, Mp, nch);
-        return hipGetLastError() == hipSuccess ? 0 : -1;
+        return with_xtype(X, xtype, [&](auto *x) {
+            using T = std::remove_cv_t<std::remove_pointer_t<decltype(x)>>;
+            if (vec) hipLaunchKernelGGL((tsg_transpose_rows_kernel<T, true>), dim3((unsigned)blocks), dim3(256), 0, s, x, XQ, M, K, Mp, nch);
+            else hipLaunchKernelGGL((tsg_transpose_rows_kernel<T, false>), dim3((unsigned)blocks), dim3(256), 0, s, x, XQ, M, K, Mp, nch);
+            return hipGetLastError() == hipSuccess ? 0 : -1;
+        });
     }
     // Mp is a multiple of 64 (the 64-row image's M tile) and Kp of 192 (its
     // chunk): the pieces cover [0, Kp) x [0, Mp) exactly
@@ -391,17 +413,19 @@ int launch_transpose_quads(const float *X, float *XQ, int M, int K, int Mp, int 
     const int units = chunk / 4;
     const int64_t blocks = (int64_t)(Kp / chunk) * (Mp / 64) * (units / 4);
     if (blocks >= ((int64_t)1 << 31)) return -1;
+    if (piece_rows != 16 && piece_rows != 8) return -1;
     dim3 grid((unsigned)blocks);
-    if (piece_rows == 16) {
-        if (vec) hipLaunchKernelGGL((tsg_transpose_quads_kernel<true, 16>), grid, dim3(256), 0, s, X, XQ, M, K, Mp, Kp, units);
-        else hipLaunchKernelGGL((tsg_transpose_quads_kernel<false, 16>), grid, dim3(256), 0, s, X, XQ, M, K, Mp, Kp, units);
-    } else if (piece_rows == 8) {
-        if (vec) hipLaunchKernelGGL((tsg_transpose_quads_kernel<true, 8>), grid, dim3(256), 0, s, X, XQ, M, K, Mp, Kp, units);
-        else hipLaunchKernelGGL((tsg_transpose_quads_kernel<false, 8>), grid, dim3(256), 0, s, X, XQ, M, K, Mp, Kp, units);
-    } else {
-        return -1;
-    }
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return with_xtype(X, xtype, [&](auto *x) {
+        using T = std::remove_cv_t<std::remove_pointer_t<decltype(x)>>;
+        if (piece_rows == 16) {
+            if (vec) hipLaunchKernelGGL((tsg_transpose_quads_kernel<T, true, 16>), grid, dim3(256), 0, s, x, XQ, M, K, Mp, Kp, units);
+            else hipLaunchKernelGGL((tsg_transpose_quads_kernel<T, false, 16>), grid, dim3(256), 0, s, x, XQ, M, K, Mp, Kp, units);
+        } else {
+            if (vec) hipLaunchKernelGGL((tsg_transpose_quads_kernel<T, true, 8>), grid, dim3(256), 0, s, x, XQ, M, K, Mp, Kp, units);
+            else hipLaunchKernelGGL((tsg_transpose_quads_kernel<T, false, 8>), grid, dim3(256), 0, s, x, XQ, M, K, Mp, Kp, units);
+        }
+        return hipGetLastError() == hipSuccess ? 0 : -1;
+    });
 }
 
 int launch_tcsc_rx(const float *XT, int Mp, const uint32_t *wstart, const uint32_t *ent,

@@ -397,7 +397,9 @@ int ensure_ell(tsg_tcsc *h, int v)
 
 // One device-pointer call, as its launch functions see it
 struct Call {
-    const float *dX, *db, *dalpha;
+    const void *dX;  // M x K row-major elements of xtype (tsg::XType)
+    int xtype;
+    const float *db, *dalpha;
     float *dY;
     int64_t ldY;  // floats from one Y row to the next (>= N)
     int M;
@@ -431,7 +433,8 @@ int work_end(tsg_tcsc *h, const Call &c)
     return TSG_OK;
 }
 
-// small M: the ELL walk reads X in place (no X^T staging, no work buffer)
+// small M: the ELL walk reads X in place, whatever its element type (no X^T
+// staging, no work buffer)
 int run_ell(tsg_tcsc *h, const CallPlan &p, const Call &c)
 {
     if (!h->ell[p.ell].ready && c.capturing)
@@ -445,10 +448,10 @@ int run_ell(tsg_tcsc *h, const CallPlan &p, const Call &c)
     const tsg_tcsc::EllVariant &e = h->ell[p.ell];
     const int N = h->plan.N, K = h->plan.K;
     const int lrc = p.kernel == Kernel::kEllPc
-                        ? tsg::launch_tcsc_ell_pc(p.ell, c.dX, e.d_ent, e.d_tab, c.db, c.dalpha, c.dY, c.ldY, c.M, N, K,
-                                                  e.img.C, e.img.nch, c.prelu ? 1 : 0, c.s)
-                        : tsg::launch_tcsc_ell(p.ell, c.dX, e.d_ent, e.d_tab, c.db, c.dalpha, c.dY, c.ldY, c.M, N, K,
-                                               e.img.C, e.img.nch, e.img.xb, e.img.zr, c.prelu ? 1 : 0, c.s);
+                        ? tsg::launch_tcsc_ell_pc(p.ell, c.dX, c.xtype, e.d_ent, e.d_tab, c.db, c.dalpha, c.dY, c.ldY,
+                                                  c.M, N, K, e.img.C, e.img.nch, c.prelu ? 1 : 0, c.s)
+                        : tsg::launch_tcsc_ell(p.ell, c.dX, c.xtype, e.d_ent, e.d_tab, c.db, c.dalpha, c.dY, c.ldY, c.M,
+                                               N, K, e.img.C, e.img.nch, e.img.xb, e.img.zr, c.prelu ? 1 : 0, c.s);
     if (lrc != 0)
         return fail(TSG_ERR_HIP, std::string("small-M kernel launch: ") + hipGetErrorString(hipGetLastError()));
     return timing_end(h, slot, c.s);
@@ -464,7 +467,7 @@ int run_rx(tsg_tcsc *h, const CallPlan &p, const Call &c)
     if (K == 0) {
         // no X at all: chain is +0; X^T stays zero
         HIP_TRY(hipMemsetAsync(h->d_work, 0, (size_t)d.Mp * d.Kp * sizeof(float), c.s));
-    } else if (tsg::launch_transpose(c.dX, h->d_work, c.M, K, d.Mp, d.Kp, c.s) != 0) {
+    } else if (tsg::launch_transpose(c.dX, c.xtype, h->d_work, c.M, K, d.Mp, d.Kp, c.s) != 0) {
         return fail(TSG_ERR_HIP, std::string("transpose launch: ") + hipGetErrorString(hipGetLastError()));
     }
     int slot;
@@ -492,7 +495,11 @@ int run_jit(tsg_tcsc *h, const CallPlan &p, const tsg_tcsc::JitVariant &jv, cons
         return fail(TSG_ERR_ARG, "M=" + std::to_string(c.M) + " is too large for one jit launch; split the rows");
     // the 64-row image stages straight from row-major X (no X^T pass, no work
     // buffer) when every row starts 16-B aligned and the offsets fit 32 bits
-    const bool direct = tsg::x_direct(h->plan, p.shape, jv.piece_rows, ((uintptr_t)c.dX & 15) == 0, c.M);
+    // (the image's DMA reads fp32: an X of another type is always staged, by
+    // the pass that widens it -- also at shapes where an fp32 X needs no work
+    // buffer, which tcsc_hip_reserve sizes for the staged copy regardless)
+    const bool direct = c.xtype == tsg::kXF32 &&
+                        tsg::x_direct(h->plan, p.shape, jv.piece_rows, ((uintptr_t)c.dX & 15) == 0, c.M);
     if (r64 && jv.chunk != p.chunk)  // the image and this call's X^T dims must agree (TSG_JIT_QBLOCK read at both)
         return fail(TSG_ERR_ARG, "64-row image built for " + std::to_string(jv.chunk) + "-row chunks, call expects " +
                                      std::to_string(p.chunk) + " (TSG_JIT_QBLOCK changed after the image was built)");
@@ -508,15 +515,17 @@ int run_jit(tsg_tcsc *h, const CallPlan &p, const tsg_tcsc::JitVariant &jv, cons
         if (K == 0) {
             // no X at all: chain is +0; X^T stays zero
             HIP_TRY(hipMemsetAsync(h->d_work, 0, (size_t)d.Mp * d.Kp * sizeof(float), c.s));
-        } else if ((r64 ? tsg::launch_transpose_quads(c.dX, h->d_work, c.M, K, d.Mp, d.Kp, jv.piece_rows, c.s, p.chunk)
-                        : tsg::launch_transpose_pairs(c.dX, h->d_work, c.M, K, d.Mp, d.Kp, c.s)) != 0) {
+        } else if ((r64 ? tsg::launch_transpose_quads(c.dX, c.xtype, h->d_work, c.M, K, d.Mp, d.Kp, jv.piece_rows, c.s,
+                                                      p.chunk)
+                        : tsg::launch_transpose_pairs(c.dX, c.xtype, h->d_work, c.M, K, d.Mp, d.Kp, c.s)) != 0) {
             return fail(TSG_ERR_HIP, std::string("transpose launch: ") + hipGetErrorString(hipGetLastError()));
         }
     }
     int slot;
     rc = timing_begin(h, c.capturing, c.s, slot);
     if (rc) return rc;
-    if (tsg::launch_tcsc_jit(jv.mod, direct ? c.dX : h->d_work, d.Mp, jv.d_wcode, c.db, c.dalpha, c.dY, c.ldY, c.M, N,
+    if (tsg::launch_tcsc_jit(jv.mod, direct ? static_cast<const float *>(c.dX) : h->d_work, d.Mp, jv.d_wcode, c.db,
+                             c.dalpha, c.dY, c.ldY, c.M, N,
                              jv.Npad, jv.nch, c.prelu ? 1 : 0, h->d_status, jv.nw * jv.waves, waves, p.gn, p.gm, p.tmask,
                              c.s, p.tile_m, direct ? K : 0, lastadj, p.xtouch, p.tnear) != 0)
         return fail(TSG_ERR_HIP, std::string("tcsc launch: ") + hipGetErrorString(hipGetLastError()));
@@ -525,10 +534,13 @@ int run_jit(tsg_tcsc *h, const CallPlan &p, const tsg_tcsc::JitVariant &jv, cons
     return work_end(h, c);
 }
 
-int run_dev(tsg_tcsc *h, const float *dX, const float *db, const float *dalpha, float *dY, int64_t ldY, int M,
-            int N, int K, hipStream_t s, bool prelu)
+int run_dev(tsg_tcsc *h, const void *dX, const float *db, const float *dalpha, float *dY, int64_t ldY, int M,
+            int N, int K, hipStream_t s, bool prelu, int xtype = tsg::kXF32)
 {
     if (!h) return fail(TSG_ERR_ARG, "null handle");
+    if (!tsg::xtype_ok(xtype))  // refused before anything is enqueued
+        return fail(TSG_ERR_ARG,
+                    "xtype=" + std::to_string(xtype) + " is not a tsg_xtype (0 fp32, 1 fp16, 2 bf16, 3 int8)");
     if (N != h->plan.N || K != h->plan.K)
         return fail(TSG_ERR_ARG, "shape mismatch: handle has K=" + std::to_string(h->plan.K) + " N=" +
                                      std::to_string(h->plan.N) + ", call has K=" + std::to_string(K) +
@@ -545,7 +557,7 @@ int run_dev(tsg_tcsc *h, const float *dX, const float *db, const float *dalpha, 
     std::lock_guard<std::mutex> lk(h->mu);
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     HIP_TRY(hipStreamIsCapturing(s, &cap));
-    const Call c{dX, db, dalpha, dY, ldY, M, s, prelu, cap != hipStreamCaptureStatusNone};
+    const Call c{dX, xtype, db, dalpha, dY, ldY, M, s, prelu, cap != hipStreamCaptureStatusNone};
     CallPlan p = tsg::plan_call(h->plan, M);
     if (p.is_ell()) return run_ell(h, p, c);
     if (!p.is_jit()) return run_rx(h, p, c);
@@ -1003,6 +1015,9 @@ extern "C" void tcsc_hip_destroy(tsg_tcsc *h) { free_handle(h); }
 // image of every shape such a call picks (tsg_plan.cpp pick_jit_shape depends
 // on M only through the number of 128-row M tiles).  After it, calls with M <=
 // max_M allocate and compile nothing, so they can be captured in a graph.
+// The work buffer is sized for the staged copy of every image whether or not
+// an fp32 call would read X directly: a call with a narrower X (run_jit)
+// always stages.
 extern "C" int tcsc_hip_reserve(tsg_tcsc *h, int max_M)
 {
     if (!h || max_M < 0) return fail(TSG_ERR_ARG, "bad reserve arguments");
@@ -1266,6 +1281,21 @@ extern "C" int tcsc_hip_gemm_prelu_dev_ld(tsg_tcsc *h, const float *dX, const fl
                                           float *dY, int64_t ldY, int M, int N, int K, void *stream)
 {
     return run_dev(h, dX, db, dalpha, dY, ldY, M, N, K, (hipStream_t)stream, true);
+}
+
+// X of another element type (tsg_xtype): the same calls, the type carried to
+// the pass that reads X (Call::xtype); TSG_X_F32 is tcsc_hip_gemm_dev_ld
+extern "C" int tcsc_hip_gemm_dev_x(tsg_tcsc *h, const void *dX, int xtype, const float *db, float *dY, int64_t ldY,
+                                   int M, int N, int K, void *stream)
+{
+    return run_dev(h, dX, db, nullptr, dY, ldY, M, N, K, (hipStream_t)stream, false, xtype);
+}
+
+extern "C" int tcsc_hip_gemm_prelu_dev_x(tsg_tcsc *h, const void *dX, int xtype, const float *db,
+                                         const float *dalpha, float *dY, int64_t ldY, int M, int N, int K,
+                                         void *stream)
+{
+    return run_dev(h, dX, db, dalpha, dY, ldY, M, N, K, (hipStream_t)stream, true, xtype);
 }
 
 extern "C" int tcsc_hip_info(const tsg_tcsc *h, tsg_info *o)

@@ -39,8 +39,10 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstdlib>
+#include <type_traits>
 
 #include "tsg_internal.h"
+#include "tsg_xtype.h"
 
 namespace tsg {
 
@@ -166,14 +168,15 @@ __device__ __forceinline__ uint32_t wave_max(uint32_t n)
 }
 
 // Stage X^T[chunk at kc][MT rows from m0] into xs ([C][MT], row-major by k)
-// with NT threads: a thread loads 4 consecutive k of one row m (16 B when
-// aligned) and writes them to 4 LDS rows; consecutive threads take
+// with NT threads: a thread loads 4 consecutive k of one row m (one load of
+// the quad when aligned) and writes them to 4 LDS rows; consecutive threads take
 // consecutive m, so the LDS writes hit consecutive banks.  SB unconditional
 // loads from clamped in-range addresses go out before their masked stores
 // (no branch between them, so no wait per load).  Rows past M and k past K
-// are +0.
-template <int MT, int NT, int SB>
-__device__ __forceinline__ void ell_stage(float *xs, const float *__restrict__ X, int M, int K, int m0, int kc, int C,
+// are +0.  X holds elements of type T (tsg_xtype.h), widened to fp32 as they
+// are loaded: xs is fp32 whatever T is.
+template <typename T, int MT, int NT, int SB>
+__device__ __forceinline__ void ell_stage(float *xs, const T *__restrict__ X, int M, int K, int m0, int kc, int C,
                                           int tid, bool vec, int xb)
 {
     const int per = C / 4 * MT;
@@ -185,7 +188,7 @@ __device__ __forceinline__ void ell_stage(float *xs, const float *__restrict__ X
                 const int i = i0 + u * NT;
                 const int mm = i % MT, r4 = (i / MT) * 4, m = m0 + mm, k = kc + r4;
                 const bool in = i < per && m < M && k + 3 < K;
-                v[u] = *reinterpret_cast<const float4 *>(X + (in ? (size_t)m * K + k : 0));
+                v[u] = xload4(X + (in ? (size_t)m * K + k : 0));
             }
 #pragma unroll
             for (int u = 0; u < SB; u++) {
@@ -212,11 +215,11 @@ __device__ __forceinline__ void ell_stage(float *xs, const float *__restrict__ X
             const int mm = i % MT, r4 = (i / MT) * 4, m = m0 + mm, k = kc + r4;
             float4 w = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
             if (m < M) {
-                const float *xr = X + (size_t)m * K + k;
-                if (k < K) w.x = xr[0];
-                if (k + 1 < K) w.y = xr[1];
-                if (k + 2 < K) w.z = xr[2];
-                if (k + 3 < K) w.w = xr[3];
+                const T *xr = X + (size_t)m * K + k;
+                if (k < K) w.x = xload1(xr);
+                if (k + 1 < K) w.y = xload1(xr + 1);
+                if (k + 2 < K) w.z = xload1(xr + 2);
+                if (k + 3 < K) w.w = xload1(xr + 3);
             }
             xs[(r4 + 0) * MT + mm] = w.x;
             xs[(r4 + 1) * MT + mm] = w.y;
@@ -234,9 +237,9 @@ __device__ __forceinline__ void ell_stage(float *xs, const float *__restrict__ X
 
 }  // namespace
 
-template <int LG, int RPL, int WPG, int LA, bool PRELU>
+template <typename T, int LG, int RPL, int WPG, int LA, bool PRELU>
 __global__ __launch_bounds__(WPG * 64) void tsg_tcsc_ell_kernel(
-    const float *__restrict__ X, const uint4 *__restrict__ ent, const uint2 *__restrict__ tab,
+    const T *__restrict__ X, const uint4 *__restrict__ ent, const uint2 *__restrict__ tab,
     const float *__restrict__ b, const float *__restrict__ alpha, float *__restrict__ Y, int64_t ldY, int M, int N,
     int K, int C, int nch, int steps, int nsg, int xb, int zr)
 {
@@ -252,7 +255,7 @@ __global__ __launch_bounds__(WPG * 64) void tsg_tcsc_ell_kernel(
     const int slice = n >> 4, c = n & 15;
     const int m0 = mt * MT;
     const int nslices = (N + 15) / 16;
-    const bool vec = K >= 4 && (K & 3) == 0 && ((((uintptr_t)X) & 15) == 0);  // X[0..3] exists
+    const bool vec = K >= 4 && (K & 3) == 0 && ((((uintptr_t)X) & (4 * sizeof(T) - 1)) == 0);  // X[0..3] exists
     const uint4 *e0 = ent + c;                       // the lane's column in block 0
     const uint32_t base = (uint32_t)(uintptr_t)(lds_f *)xs + (uint32_t)(g * RPL * 4);
 
@@ -291,7 +294,7 @@ __global__ __launch_bounds__(WPG * 64) void tsg_tcsc_ell_kernel(
         const int j = steps == 1 ? 0 : step % nch, kc = j * C;
         if (step == 0 || steps > 1) {
             __syncthreads();  // previous chunk's reads are done
-            ell_stage<MT, WPG * 64, SB>(xs, X, M, K, m0, kc, C, tid, vec, xb);
+            ell_stage<T, MT, WPG * 64, SB>(xs, X, M, K, m0, kc, C, tid, vec, xb);
             __syncthreads();
         }
         ell_walk<RPL, D, LA>(y, q, e0, off, n8, n8pos, nmax, base);
@@ -348,9 +351,9 @@ struct PcShape {
 
 }  // namespace
 
-template <int MT, int E, bool PRELU>
+template <typename T, int MT, int E, bool PRELU>
 __global__ __launch_bounds__(64 * (MT + E / 8)) void tsg_tcsc_ell_pc_kernel(
-    const float *__restrict__ X, const uint4 *__restrict__ ent, const uint2 *__restrict__ tab,
+    const T *__restrict__ X, const uint4 *__restrict__ ent, const uint2 *__restrict__ tab,
     const float *__restrict__ b, const float *__restrict__ alpha, float *__restrict__ Y, int64_t ldY, int M, int N,
     int K, int C, int nsg)
 {
@@ -396,8 +399,8 @@ __global__ __launch_bounds__(64 * (MT + E / 8)) void tsg_tcsc_ell_pc_kernel(
         for (int d = 0; d < D; d++) q[d] = load(d);
     }
     for (int i = tid; i < MT; i += S::NT) xs[C * MT + i] = 0.0f;  // the zero row
-    const bool vec = K >= 4 && (K & 3) == 0 && ((((uintptr_t)X) & 15) == 0);
-    ell_stage<MT, S::NT, 8>(xs, X, M, K, m0, 0, C, tid, vec, 0);
+    const bool vec = K >= 4 && (K & 3) == 0 && ((((uintptr_t)X) & (4 * sizeof(T) - 1)) == 0);
+    ell_stage<T, MT, S::NT, 8>(xs, X, M, K, m0, 0, C, tid, vec, 0);
     lds_barrier();
 
     if (consumer) {
@@ -528,8 +531,8 @@ __global__ __launch_bounds__(64 * (MT + E / 8)) void tsg_tcsc_ell_pc_kernel(
 
 namespace {
 
-template <int LG, int RPL, int WPG, int LA>
-int launch_ell_la(const float *X, const uint4 *ent, const uint2 *tab, const float *b, const float *alpha, float *Y,
+template <typename T, int LG, int RPL, int WPG, int LA>
+int launch_ell_la(const T *X, const uint4 *ent, const uint2 *tab, const float *b, const float *alpha, float *Y,
                   int64_t ldY, int M, int N, int K, int C, int nch, int xb, int zr, int prelu, hipStream_t s)
 {
     constexpr int MT = LG * RPL, CPW = 64 / LG;
@@ -539,10 +542,10 @@ int launch_ell_la(const float *X, const uint4 *ent, const uint2 *tab, const floa
     const size_t lds = ell_lds_floats(C, MT, xb, zr) * sizeof(float);
     const dim3 grid((unsigned)(nsg * mtiles)), block(WPG * 64);
     if (prelu)
-        hipLaunchKernelGGL((tsg_tcsc_ell_kernel<LG, RPL, WPG, LA, true>), grid, block, lds, s, X, ent, tab, b, alpha,
+        hipLaunchKernelGGL((tsg_tcsc_ell_kernel<T, LG, RPL, WPG, LA, true>), grid, block, lds, s, X, ent, tab, b, alpha,
                            Y, ldY, M, N, K, C, nch, steps, nsg, xb, zr);
     else
-        hipLaunchKernelGGL((tsg_tcsc_ell_kernel<LG, RPL, WPG, LA, false>), grid, block, lds, s, X, ent, tab, b, alpha,
+        hipLaunchKernelGGL((tsg_tcsc_ell_kernel<T, LG, RPL, WPG, LA, false>), grid, block, lds, s, X, ent, tab, b, alpha,
                            Y, ldY, M, N, K, C, nch, steps, nsg, xb, zr);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
@@ -558,13 +561,13 @@ int pick_la()
     return env ? env : 1;
 }
 
-template <int LG, int RPL, int WPG>
-int launch_ell_t(const float *X, const uint4 *ent, const uint2 *tab, const float *b, const float *alpha, float *Y,
+template <typename T, int LG, int RPL, int WPG>
+int launch_ell_t(const T *X, const uint4 *ent, const uint2 *tab, const float *b, const float *alpha, float *Y,
                  int64_t ldY, int M, int N, int K, int C, int nch, int xb, int zr, int prelu, hipStream_t s)
 {
     if (pick_la() == 2)
-        return launch_ell_la<LG, RPL, WPG, 2>(X, ent, tab, b, alpha, Y, ldY, M, N, K, C, nch, xb, zr, prelu, s);
-    return launch_ell_la<LG, RPL, WPG, 1>(X, ent, tab, b, alpha, Y, ldY, M, N, K, C, nch, xb, zr, prelu, s);
+        return launch_ell_la<T, LG, RPL, WPG, 2>(X, ent, tab, b, alpha, Y, ldY, M, N, K, C, nch, xb, zr, prelu, s);
+    return launch_ell_la<T, LG, RPL, WPG, 1>(X, ent, tab, b, alpha, Y, ldY, M, N, K, C, nch, xb, zr, prelu, s);
 }
 
 }  // namespace
@@ -584,8 +587,8 @@ namespace {
 // rows (more spill at 8 and 16 waves).  TSG_ELL_WPG=4/8/16 forces one (A/B).
 constexpr int64_t kEllWideWgs = 224;  // 7/8 of the CUs
 
-template <int LG, int RPL>
-int launch_lg(const float *X, const uint4 *e, const uint2 *t, const float *b, const float *alpha, float *Y,
+template <typename T, int LG, int RPL>
+int launch_lg(const T *X, const uint4 *e, const uint2 *t, const float *b, const float *alpha, float *Y,
               int64_t ldY, int M, int N, int K, int C, int nch, int xb, int zr, int prelu, hipStream_t s)
 {
     constexpr int MT = LG * RPL, CPW = 64 / LG;
@@ -595,11 +598,11 @@ int launch_lg(const float *X, const uint4 *e, const uint2 *t, const float *b, co
         const char *v = knob_value("TSG_ELL_WPG");
         return v ? atoi(v) : 0;
     }();
-    if (env_wpg == 4) return launch_ell_t<LG, RPL, 4>(X, e, t, b, alpha, Y, ldY, M, N, K, C, nch, xb, zr, prelu, s);
+    if (env_wpg == 4) return launch_ell_t<T, LG, RPL, 4>(X, e, t, b, alpha, Y, ldY, M, N, K, C, nch, xb, zr, prelu, s);
     if constexpr (RPL <= 2) {
-        if (env_wpg == 8) return launch_ell_t<LG, RPL, 8>(X, e, t, b, alpha, Y, ldY, M, N, K, C, nch, xb, zr, prelu, s);
+        if (env_wpg == 8) return launch_ell_t<T, LG, RPL, 8>(X, e, t, b, alpha, Y, ldY, M, N, K, C, nch, xb, zr, prelu, s);
         if (env_wpg == 16)
-            return launch_ell_t<LG, RPL, 16>(X, e, t, b, alpha, Y, ldY, M, N, K, C, nch, xb, zr, prelu, s);
+            return launch_ell_t<T, LG, RPL, 16>(X, e, t, b, alpha, Y, ldY, M, N, K, C, nch, xb, zr, prelu, s);
     }
     if constexpr (RPL <= 2) {
         auto one_round = [&](int64_t wpg) {  // >= 7/8 of the CUs busy, no second round
@@ -607,14 +610,14 @@ int launch_lg(const float *X, const uint4 *e, const uint2 *t, const float *b, co
             return wgs >= kEllWideWgs && wgs <= 256 * per_cu;
         };
         if (one_round(16))
-            return launch_ell_t<LG, RPL, 16>(X, e, t, b, alpha, Y, ldY, M, N, K, C, nch, xb, zr, prelu, s);
-        if (one_round(8)) return launch_ell_t<LG, RPL, 8>(X, e, t, b, alpha, Y, ldY, M, N, K, C, nch, xb, zr, prelu, s);
+            return launch_ell_t<T, LG, RPL, 16>(X, e, t, b, alpha, Y, ldY, M, N, K, C, nch, xb, zr, prelu, s);
+        if (one_round(8)) return launch_ell_t<T, LG, RPL, 8>(X, e, t, b, alpha, Y, ldY, M, N, K, C, nch, xb, zr, prelu, s);
         if (waves > 256 * per_cu * 8)
-            return launch_ell_t<LG, RPL, 16>(X, e, t, b, alpha, Y, ldY, M, N, K, C, nch, xb, zr, prelu, s);
+            return launch_ell_t<T, LG, RPL, 16>(X, e, t, b, alpha, Y, ldY, M, N, K, C, nch, xb, zr, prelu, s);
         if (waves > 256 * per_cu * 4)
-            return launch_ell_t<LG, RPL, 8>(X, e, t, b, alpha, Y, ldY, M, N, K, C, nch, xb, zr, prelu, s);
+            return launch_ell_t<T, LG, RPL, 8>(X, e, t, b, alpha, Y, ldY, M, N, K, C, nch, xb, zr, prelu, s);
     }
-    return launch_ell_t<LG, RPL, 4>(X, e, t, b, alpha, Y, ldY, M, N, K, C, nch, xb, zr, prelu, s);
+    return launch_ell_t<T, LG, RPL, 4>(X, e, t, b, alpha, Y, ldY, M, N, K, C, nch, xb, zr, prelu, s);
 }
 
 // lanes per column of an M tile: the default, or TSG_ELL_LG (diagnostic sweeps)
@@ -633,8 +636,8 @@ constexpr size_t pc_lds(int C)
     return ((size_t)((C + 1) * MT + 3) / 4 * 4) * sizeof(float) + (size_t)3 * (E / 4) * PcShape<MT, E>::CH * 16;
 }
 
-template <int MT, int E>
-int launch_pc_t(const float *X, const uint4 *ent, const uint2 *tab, const float *b, const float *alpha, float *Y,
+template <typename T, int MT, int E>
+int launch_pc_t(const T *X, const uint4 *ent, const uint2 *tab, const float *b, const float *alpha, float *Y,
                 int64_t ldY, int M, int N, int K, int C, int prelu, hipStream_t s)
 {
     using S = PcShape<MT, E>;
@@ -643,10 +646,10 @@ int launch_pc_t(const float *X, const uint4 *ent, const uint2 *tab, const float 
     const size_t lds = pc_lds<MT, E>(C);
     const dim3 grid((unsigned)(nsg * mtiles)), block(S::NT);
     if (prelu)
-        hipLaunchKernelGGL((tsg_tcsc_ell_pc_kernel<MT, E, true>), grid, block, lds, s, X, ent, tab, b, alpha, Y, ldY, M,
+        hipLaunchKernelGGL((tsg_tcsc_ell_pc_kernel<T, MT, E, true>), grid, block, lds, s, X, ent, tab, b, alpha, Y, ldY, M,
                            N, K, C, nsg);
     else
-        hipLaunchKernelGGL((tsg_tcsc_ell_pc_kernel<MT, E, false>), grid, block, lds, s, X, ent, tab, b, alpha, Y, ldY,
+        hipLaunchKernelGGL((tsg_tcsc_ell_pc_kernel<T, MT, E, false>), grid, block, lds, s, X, ent, tab, b, alpha, Y, ldY,
                            M, N, K, C, nsg);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
@@ -689,7 +692,7 @@ size_t ell_pc_lds_bytes(int variant, int C)
     return variant == 0 ? pc_lds<1, 32>(C) : 0;
 }
 
-int launch_tcsc_ell_pc(int variant, const float *X, const uint32_t *ent, const uint32_t *tab, const float *b,
+int launch_tcsc_ell_pc(int variant, const void *X, int xtype, const uint32_t *ent, const uint32_t *tab, const float *b,
                        const float *alpha, float *Y, int64_t ldY, int M, int N, int K, int C, int nch, int prelu,
                        void *stream)
 {
@@ -698,27 +701,28 @@ int launch_tcsc_ell_pc(int variant, const float *X, const uint32_t *ent, const u
     hipStream_t s = (hipStream_t)stream;
     const uint4 *e = reinterpret_cast<const uint4 *>(ent);
     const uint2 *t = reinterpret_cast<const uint2 *>(tab);
-    switch (pc_phase(M, N, C)) {
-    case 16: return launch_pc_t<1, 16>(X, e, t, b, alpha, Y, ldY, M, N, K, C, prelu, s);
-    case 64: return launch_pc_t<1, 64>(X, e, t, b, alpha, Y, ldY, M, N, K, C, prelu, s);
-    default: return launch_pc_t<1, 32>(X, e, t, b, alpha, Y, ldY, M, N, K, C, prelu, s);  // 1 consumer, 4 producers
-    }
+    const int phase = pc_phase(M, N, C);
+    return with_xtype(X, xtype, [&](auto *x) {
+        using T = std::remove_cv_t<std::remove_pointer_t<decltype(x)>>;
+        switch (phase) {
+        case 16: return launch_pc_t<T, 1, 16>(x, e, t, b, alpha, Y, ldY, M, N, K, C, prelu, s);
+        case 64: return launch_pc_t<T, 1, 64>(x, e, t, b, alpha, Y, ldY, M, N, K, C, prelu, s);
+        default: return launch_pc_t<T, 1, 32>(x, e, t, b, alpha, Y, ldY, M, N, K, C, prelu, s);  // 1 consumer, 4 producers
+        }
+    });
 }
 
-int launch_tcsc_ell(int variant, const float *X, const uint32_t *ent, const uint32_t *tab, const float *b,
-                    const float *alpha, float *Y, int64_t ldY, int M, int N, int K, int C, int nch, int xb, int zr,
-                    int prelu, void *stream)
+namespace {
+
+template <typename T>
+int launch_ell_variant(int variant, const T *X, const uint4 *e, const uint2 *t, const float *b, const float *alpha,
+                       float *Y, int64_t ldY, int M, int N, int K, int C, int nch, int xb, int zr, int prelu,
+                       hipStream_t s)
 {
-    // the second X^T copy and the bank-window schedule serve the 8-row tile's
-    // 4-lane columns only (tsg_host.cpp build_ell_image)
-    if ((xb || zr != 1) && (variant != 2 || pick_lg(4) != 4)) return -2;
-    hipStream_t s = (hipStream_t)stream;
-    const uint4 *e = reinterpret_cast<const uint4 *>(ent);
-    const uint2 *t = reinterpret_cast<const uint2 *>(tab);
 #define TSG_ELL_LG(lg, rpl) \
-    case lg: return launch_lg<lg, rpl>(X, e, t, b, alpha, Y, ldY, M, N, K, C, nch, xb, zr, prelu, s)
+    case lg: return launch_lg<T, lg, rpl>(X, e, t, b, alpha, Y, ldY, M, N, K, C, nch, xb, zr, prelu, s)
     switch (variant) {
-    case 0: return launch_ell_t<1, 1, 1>(X, e, t, b, alpha, Y, ldY, M, N, K, C, nch, xb, zr, prelu, s);  // MT = 1
+    case 0: return launch_ell_t<T, 1, 1, 1>(X, e, t, b, alpha, Y, ldY, M, N, K, C, nch, xb, zr, prelu, s);  // MT = 1
     case 1:                                                                                   // MT = 4
         switch (pick_lg(4)) {
             TSG_ELL_LG(4, 1);
@@ -746,6 +750,23 @@ int launch_tcsc_ell(int variant, const float *X, const uint32_t *ent, const uint
     default: return -2;
     }
 #undef TSG_ELL_LG
+}
+
+}  // namespace
+
+int launch_tcsc_ell(int variant, const void *X, int xtype, const uint32_t *ent, const uint32_t *tab, const float *b,
+                    const float *alpha, float *Y, int64_t ldY, int M, int N, int K, int C, int nch, int xb, int zr,
+                    int prelu, void *stream)
+{
+    // the second X^T copy and the bank-window schedule serve the 8-row tile's
+    // 4-lane columns only (tsg_host.cpp build_ell_image)
+    if ((xb || zr != 1) && (variant != 2 || pick_lg(4) != 4)) return -2;
+    hipStream_t s = (hipStream_t)stream;
+    const uint4 *e = reinterpret_cast<const uint4 *>(ent);
+    const uint2 *t = reinterpret_cast<const uint2 *>(tab);
+    return with_xtype(X, xtype, [&](auto *x) {
+        return launch_ell_variant(variant, x, e, t, b, alpha, Y, ldY, M, N, K, C, nch, xb, zr, prelu, s);
+    });
 }
 
 }  // namespace tsg

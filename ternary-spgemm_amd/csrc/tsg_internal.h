@@ -11,6 +11,18 @@ namespace tsg {
 
 constexpr int kLanes = 64;                     // wavefront width (CDNA)
 
+// Element type of the caller's X on the device-pointer calls (tsg_xtype,
+// include/ternary_spgemm.h).  Only the kernels that read the caller's X see
+// it -- the staging passes and the two small-M walks, which widen to fp32 on
+// load (tsg_xtype.h); work buffers, LDS and the weight-compiled images hold
+// fp32 whatever the type, and the planner does not look at it.
+enum XType { kXF32 = 0, kXF16 = 1, kXBF16 = 2, kXI8 = 3 };
+inline bool xtype_ok(int xtype) { return xtype >= kXF32 && xtype <= kXI8; }
+inline size_t xtype_size(int xtype) { return xtype == kXF32 ? 4 : xtype == kXI8 ? 1 : 2; }
+// X starts on a multiple of 4 elements: with K % 4 == 0 every quad of every
+// row then does, and the staging passes load a quad at a time
+inline bool x_quad_aligned(const void *X, int xtype) { return ((uintptr_t)X & (4 * xtype_size(xtype) - 1)) == 0; }
+
 // ---------------------------------------------------------------------------
 // "rx" (register-X) kernel (tsg_tcsc_rx_kernel)
 //
@@ -269,7 +281,7 @@ __host__ __device__ constexpr int ell_lds_floats(int C, int MT, int xb, int zr =
 constexpr int kEllSchedZeroRows = 8;
 void build_ell_image(const int32_t *csp, const int32_t *csn, const int32_t *rip, const int32_t *rin, int K, int N,
                      int Cmax, int MT, EllImage &img, int copies = 1, bool sched = false);
-int launch_tcsc_ell(int variant, const float *X, const uint32_t *ent, const uint32_t *tab, const float *b,
+int launch_tcsc_ell(int variant, const void *X, int xtype, const uint32_t *ent, const uint32_t *tab, const float *b,
                     const float *alpha, float *Y, int64_t ldY, int M, int N, int K, int C, int nch, int xb, int zr,
                     int prelu, void *stream);
 // the producer/consumer walk (tsg_tcsc_ell_pc_kernel) of variant 0 (M = 1) when
@@ -277,7 +289,7 @@ int launch_tcsc_ell(int variant, const float *X, const uint32_t *ent, const uint
 // (ell_pc_lds_bytes; 0 = no such variant); -2 = not available for this image
 constexpr size_t kLdsBytes = 160 * 1024;
 size_t ell_pc_lds_bytes(int variant, int C);
-int launch_tcsc_ell_pc(int variant, const float *X, const uint32_t *ent, const uint32_t *tab, const float *b,
+int launch_tcsc_ell_pc(int variant, const void *X, int xtype, const uint32_t *ent, const uint32_t *tab, const float *b,
                        const float *alpha, float *Y, int64_t ldY, int M, int N, int K, int C, int nch, int prelu,
                        void *stream);
 
@@ -303,15 +315,16 @@ int encode_count(const int32_t *dW, int K, int N, int32_t *d_csp, int32_t *d_csn
 int encode_fill(const int32_t *dW, int K, int N, const int32_t *d_csp, const int32_t *d_csn, int32_t *d_rip,
                 int32_t *d_rin, void *stream);
 
-// Kernel launchers (csrc/tcsc_kernels.hip).  All enqueue on `stream`.
-int launch_transpose(const float *X, float *XT, int M, int K, int Mp, int Kp, void *stream);
+// Kernel launchers (csrc/tcsc_kernels.hip).  All enqueue on `stream`.  X is M x
+// K row-major of element type xtype (XType); the staged copies are fp32.
+int launch_transpose(const void *X, int xtype, float *XT, int M, int K, int Mp, int Kp, void *stream);
 // X [M][K] -> X^T in the k-pair layout of the jit kernel (Kp even, Mp even)
-int launch_transpose_pairs(const float *X, float *XP, int M, int K, int Mp, int Kp, void *stream);
+int launch_transpose_pairs(const void *X, int xtype, float *XP, int M, int K, int Mp, int Kp, void *stream);
 // X [M][K] -> the blocked k-quad layout of the 64-row image (Mp % 64 == 0, Kp % 192 == 0;
 // piece_rows 16 or 8, kJit64R16Flag), or with piece_rows 0 its row layout's
 // staged copy (kJit64RowFlag; Kp % 188 == 0)
-int launch_transpose_quads(const float *X, float *XQ, int M, int K, int Mp, int Kp, int piece_rows, void *stream,
-                           int chunk = kJit64Chunk);
+int launch_transpose_quads(const void *X, int xtype, float *XQ, int M, int K, int Mp, int Kp, int piece_rows,
+                           void *stream, int chunk = kJit64Chunk);
 int launch_tcsc_rx(const float *XT, int Mp, const uint32_t *wstart, const uint32_t *ent,
                    const float *b, const float *alpha, float *Y, int64_t ldY, int M, int N, int Npad, int nch,
                    int prelu, void *stream);

@@ -49,7 +49,11 @@ EXPORTED_SYMBOLS = (
     "tsg_jit_codegen_far", "tsg_call_plan", "tsg_call_xtouch", "tsg_knob_check", "tcsc_hip_set_tile_rows", "tcsc_hip_call_tile_rows",
     "tsg_jit_codegen64", "tsg_jit_codegen64h", "tcsc_hip_call_launches",
     "tcsc_hip_gemm_dev_ld", "tcsc_hip_gemm_prelu_dev_ld",
+    "tcsc_hip_gemm_dev_x", "tcsc_hip_gemm_prelu_dev_x",
 )
+
+# enum tsg_xtype (include/ternary_spgemm.h): element type of X on the _x calls
+TSG_X_F32, TSG_X_F16, TSG_X_BF16, TSG_X_I8 = 0, 1, 2, 3
 
 
 class TSGError(RuntimeError):
@@ -101,6 +105,8 @@ def lib() -> C.CDLL:
     L.tcsc_hip_gemm_prelu_dev.argtypes = [H, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]
     L.tcsc_hip_gemm_dev_ld.argtypes = [H, vp, vp, vp, C.c_int64, C.c_int, C.c_int, C.c_int, vp]
     L.tcsc_hip_gemm_prelu_dev_ld.argtypes = [H, vp, vp, vp, vp, C.c_int64, C.c_int, C.c_int, C.c_int, vp]
+    L.tcsc_hip_gemm_dev_x.argtypes = [H, vp, C.c_int, vp, vp, C.c_int64, C.c_int, C.c_int, C.c_int, vp]
+    L.tcsc_hip_gemm_prelu_dev_x.argtypes = [H, vp, C.c_int, vp, vp, vp, C.c_int64, C.c_int, C.c_int, C.c_int, vp]
     L.tcsc_hip_reserve.argtypes = [H, C.c_int]
     L.tcsc_hip_info.argtypes = [H, C.POINTER(tsg_info)]
     L.tcsc_hip_to_dense.argtypes = [H, vp, C.c_int, C.c_int]
@@ -611,6 +617,63 @@ class TCSCDevice:
         else:
             _check(lib().tcsc_hip_gemm_prelu_dev(self._h, dX, db, dalpha, dY, M, self.N, self.K,
                                                  stream or None), "tcsc_hip_gemm_prelu_dev")
+
+    def gemm_dev_x(self, dX: int, xtype: int, db: int, dY: int, M: int, stream: int = 0,
+                   dalpha: Optional[int] = None, ldY: Optional[int] = None) -> None:
+        """gemm_dev with X in the element type xtype names (TSG_X_F32 / _F16 /
+        _BF16 / _I8; tcsc_hip_gemm_dev_x): dX is M x K row-major of that type;
+        b, alpha and Y stay fp32.  ldY None = the dense [M, N] block."""
+        ld = self.N if ldY is None else int(ldY)
+        if dalpha is None:
+            _check(lib().tcsc_hip_gemm_dev_x(self._h, dX, int(xtype), db, dY, ld, M, self.N, self.K, stream or None),
+                   "tcsc_hip_gemm_dev_x")
+        else:
+            _check(lib().tcsc_hip_gemm_prelu_dev_x(self._h, dX, int(xtype), db, dalpha, dY, ld, M, self.N, self.K,
+                                                   stream or None), "tcsc_hip_gemm_prelu_dev_x")
+
+    def gemm_torch_x(self, X, b, Y=None, alpha=None):
+        """gemm_torch_into for an X of any supported element type: X is a
+        contiguous [M, K] float32, float16, bfloat16 or int8 tensor on the
+        handle's device and goes in as it is (no fp32 copy; the library widens
+        it, exactly, in the pass that reads it), so the result is
+        gemm_torch(X.float(), b) bit for bit.  b and alpha are float32; Y is
+        None (a new contiguous [M, N] float32 tensor) or a strided output as in
+        gemm_torch_into.  Returns Y."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        xtypes = {torch.float32: TSG_X_F32, torch.float16: TSG_X_F16, torch.bfloat16: TSG_X_BF16,
+                  torch.int8: TSG_X_I8}
+        if not (isinstance(X, torch.Tensor) and X.dim() == 2 and X.shape[1] == self.K):
+            raise TSGError(1, "gemm_torch_x", f"X must be a [M, {self.K}] tensor, got "
+                                              f"{tuple(X.shape) if isinstance(X, torch.Tensor) else type(X)}")
+        M = X.shape[0]
+        if X.dtype not in xtypes or X.device != dev or not X.is_contiguous():
+            raise TSGError(1, "gemm_torch_x", f"X must be a contiguous float32, float16, bfloat16 or int8 "
+                                              f"{[M, self.K]} tensor on {dev}, got {X.dtype} {list(X.shape)} on "
+                                              f"{X.device}{'' if X.is_contiguous() else ' (non-contiguous)'}")
+        for name, t, shape in (("b", b, (self.N,)), ("alpha", alpha, (self.N,))):
+            if t is None:
+                continue
+            if t.dtype != torch.float32 or t.device != dev or not t.is_contiguous() or tuple(t.shape) != shape:
+                raise TSGError(1, "gemm_torch_x", f"{name} must be a contiguous float32 {list(shape)} tensor on "
+                                                  f"{dev}, got {t.dtype} {list(t.shape)} on {t.device}"
+                                                  f"{'' if t.is_contiguous() else ' (non-contiguous)'}")
+        if Y is None:
+            Y = torch.empty((M, self.N), dtype=torch.float32, device=dev)
+        if not isinstance(Y, torch.Tensor) or Y.dtype != torch.float32 or Y.device != dev or \
+                tuple(Y.shape) != (M, self.N):
+            got = (Y.dtype, list(Y.shape), Y.device) if isinstance(Y, torch.Tensor) else type(Y)
+            raise TSGError(1, "gemm_torch_x", f"Y must be a float32 [{M}, {self.N}] tensor on {dev}, got {got}")
+        if self.N > 1 and Y.stride(1) != 1:
+            raise TSGError(1, "gemm_torch_x", f"Y's rows must be contiguous (stride(1) == 1), got {Y.stride()}")
+        # one row has no next row: any row stride describes it
+        ldY = self.N if M <= 1 else Y.stride(0)
+        if ldY < self.N:
+            raise TSGError(1, "gemm_torch_x", f"Y's rows overlap: stride(0) = {ldY} < N = {self.N}")
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        self.gemm_dev_x(X.data_ptr(), xtypes[X.dtype], b.data_ptr(), Y.data_ptr(), M, stream,
+                        None if alpha is None else alpha.data_ptr(), ldY=ldY)
+        return Y
 
     def gemm_torch(self, X, b, Y=None, alpha=None):
         """X [M,K] fp32 cuda tensor -> Y [M,N], enqueued on torch's current stream.
