@@ -205,6 +205,45 @@ int tcsc_hip_gemm_prelu_dev_x(tsg_tcsc *h, const void *dX, int xtype, const floa
                               const float *dalpha, float *dY, int64_t ldY, int M, int N, int K,
                               void *stream);
 
+/* The same two calls again with Y in a narrower element type as well: a layer
+ * that keeps its activations in 16 bits gets them back in 16 bits from the one
+ * call, without a cast pass over an fp32 Y.  dY is M rows of the type ytype
+ * names; b and alpha stay fp32; xtype and ytype are independent.  The chain,
+ * + b[n] and the PReLU run in fp32 exactly as on tcsc_hip_gemm_dev_x, and the
+ * rounding is the last step before the store, so
+ *
+ *   Y[m, n] is the value tcsc_hip_gemm_dev_x / _prelu_dev_x would have stored,
+ *   rounded ONCE, to nearest even, to the type: bit for bit the element-wise
+ *   round-to-nearest-even cast of the fp32 call's Y.
+ *
+ * Values beyond the type's largest finite value round to +-inf (fp16: from
+ * 65520), fp16 subnormal results are kept, not flushed, -0 stays -0, and a NaN
+ * stays a NaN (its payload is not promised, as elsewhere in this library).
+ * ldY counts ELEMENTS OF THE Y TYPE and must be >= N (else TSG_ERR_ARG, nothing
+ * enqueued).  dY needs only element alignment (2 bytes for the 16-bit types),
+ * so it may be any slice of a wider buffer.  Only the elements
+ * [m * ldY, m * ldY + N) of each row are written -- and that holds for the
+ * 16-bit neighbour that shares a dword with a row's first or last element too:
+ * it is never written, not even with its own value.  A row segment that starts
+ * 16-byte aligned and is full width (a lane's 8 to 128 columns inside N) is
+ * stored with 16-byte stores of 8 elements; anything else -- the ragged last
+ * column tile, rows of an odd ldY or a misaligned dY -- element by element
+ * with 2-byte stores; the result is the same bit for bit.
+ * TSG_Y_F32 is tcsc_hip_gemm_dev_x itself (the same path, ldY in floats).  Any
+ * other ytype value returns TSG_ERR_ARG with a message naming tsg_ytype and
+ * enqueues nothing.  Stream semantics, tcsc_hip_reserve and graph capture, the
+ * kernel and image an M picks, the direct-X path of the 64-row image and the
+ * work buffer are as on tcsc_hip_gemm_dev_x: the Y type adds no allocation and
+ * no launch.  The host-pointer calls stay fp32.  Extension: no reference
+ * counterpart. */
+enum tsg_ytype { TSG_Y_F32 = 0, TSG_Y_F16 = 1, TSG_Y_BF16 = 2 };
+
+int tcsc_hip_gemm_dev_xy(tsg_tcsc *h, const void *dX, int xtype, const float *db, void *dY,
+                         int ytype, int64_t ldY, int M, int N, int K, void *stream);
+int tcsc_hip_gemm_prelu_dev_xy(tsg_tcsc *h, const void *dX, int xtype, const float *db,
+                               const float *dalpha, void *dY, int ytype, int64_t ldY, int M, int N,
+                               int K, void *stream);
+
 /* Pre-allocates the per-handle work buffer for row counts up to max_M and, on
  * the weight-compiled kernel, compiles every code image a call with M <= max_M
  * rows runs (and the small-M images), so no later such call allocates or

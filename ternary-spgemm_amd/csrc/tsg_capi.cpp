@@ -400,8 +400,9 @@ struct Call {
     const void *dX;  // M x K row-major elements of xtype (tsg::XType)
     int xtype;
     const float *db, *dalpha;
-    float *dY;
-    int64_t ldY;  // floats from one Y row to the next (>= N)
+    void *dY;     // elements of ytype (tsg::YType)
+    int ytype;
+    int64_t ldY;  // elements of ytype from one Y row to the next (>= N)
     int M;
     hipStream_t s;
     bool prelu, capturing;
@@ -448,10 +449,10 @@ int run_ell(tsg_tcsc *h, const CallPlan &p, const Call &c)
     const tsg_tcsc::EllVariant &e = h->ell[p.ell];
     const int N = h->plan.N, K = h->plan.K;
     const int lrc = p.kernel == Kernel::kEllPc
-                        ? tsg::launch_tcsc_ell_pc(p.ell, c.dX, c.xtype, e.d_ent, e.d_tab, c.db, c.dalpha, c.dY, c.ldY,
-                                                  c.M, N, K, e.img.C, e.img.nch, c.prelu ? 1 : 0, c.s)
-                        : tsg::launch_tcsc_ell(p.ell, c.dX, c.xtype, e.d_ent, e.d_tab, c.db, c.dalpha, c.dY, c.ldY, c.M,
-                                               N, K, e.img.C, e.img.nch, e.img.xb, e.img.zr, c.prelu ? 1 : 0, c.s);
+                        ? tsg::launch_tcsc_ell_pc(p.ell, c.dX, c.xtype, e.d_ent, e.d_tab, c.db, c.dalpha, c.dY, c.ytype,
+                                                  c.ldY,                                                  c.M, N, K, e.img.C, e.img.nch, c.prelu ? 1 : 0, c.s)
+                        : tsg::launch_tcsc_ell(p.ell, c.dX, c.xtype, e.d_ent, e.d_tab, c.db, c.dalpha, c.dY, c.ytype, c.ldY,
+                                               c.M,                                               N, K, e.img.C, e.img.nch, e.img.xb, e.img.zr, c.prelu ? 1 : 0, c.s);
     if (lrc != 0)
         return fail(TSG_ERR_HIP, std::string("small-M kernel launch: ") + hipGetErrorString(hipGetLastError()));
     return timing_end(h, slot, c.s);
@@ -473,8 +474,8 @@ int run_rx(tsg_tcsc *h, const CallPlan &p, const Call &c)
     int slot;
     rc = timing_begin(h, c.capturing, c.s, slot);
     if (rc) return rc;
-    if (tsg::launch_tcsc_rx(h->d_work, d.Mp, h->d_seg, h->d_ent, c.db, c.dalpha, c.dY, c.ldY, c.M, N, h->rimg.Npad,
-                            h->rimg.nch, c.prelu ? 1 : 0, c.s) != 0)
+    if (tsg::launch_tcsc_rx(h->d_work, d.Mp, h->d_seg, h->d_ent, c.db, c.dalpha, c.dY, c.ytype, c.ldY, c.M, N,
+                            h->rimg.Npad, h->rimg.nch, c.prelu ? 1 : 0, c.s) != 0)
         return fail(TSG_ERR_HIP, std::string("tcsc launch: ") + hipGetErrorString(hipGetLastError()));
     rc = timing_end(h, slot, c.s);
     return rc ? rc : work_end(h, c);
@@ -525,7 +526,7 @@ int run_jit(tsg_tcsc *h, const CallPlan &p, const tsg_tcsc::JitVariant &jv, cons
     rc = timing_begin(h, c.capturing, c.s, slot);
     if (rc) return rc;
     if (tsg::launch_tcsc_jit(jv.mod, direct ? static_cast<const float *>(c.dX) : h->d_work, d.Mp, jv.d_wcode, c.db,
-                             c.dalpha, c.dY, c.ldY, c.M, N,
+                             c.dalpha, c.dY, c.ytype, c.ldY, c.M, N,
                              jv.Npad, jv.nch, c.prelu ? 1 : 0, h->d_status, jv.nw * jv.waves, waves, p.gn, p.gm, p.tmask,
                              c.s, p.tile_m, direct ? K : 0, lastadj, p.xtouch, p.tnear) != 0)
         return fail(TSG_ERR_HIP, std::string("tcsc launch: ") + hipGetErrorString(hipGetLastError()));
@@ -534,13 +535,15 @@ int run_jit(tsg_tcsc *h, const CallPlan &p, const tsg_tcsc::JitVariant &jv, cons
     return work_end(h, c);
 }
 
-int run_dev(tsg_tcsc *h, const void *dX, const float *db, const float *dalpha, float *dY, int64_t ldY, int M,
-            int N, int K, hipStream_t s, bool prelu, int xtype = tsg::kXF32)
+int run_dev(tsg_tcsc *h, const void *dX, const float *db, const float *dalpha, void *dY, int64_t ldY, int M,
+            int N, int K, hipStream_t s, bool prelu, int xtype = tsg::kXF32, int ytype = tsg::kYF32)
 {
     if (!h) return fail(TSG_ERR_ARG, "null handle");
     if (!tsg::xtype_ok(xtype))  // refused before anything is enqueued
         return fail(TSG_ERR_ARG,
                     "xtype=" + std::to_string(xtype) + " is not a tsg_xtype (0 fp32, 1 fp16, 2 bf16, 3 int8)");
+    if (!tsg::ytype_ok(ytype))  // likewise
+        return fail(TSG_ERR_ARG, "ytype=" + std::to_string(ytype) + " is not a tsg_ytype (0 fp32, 1 fp16, 2 bf16)");
     if (N != h->plan.N || K != h->plan.K)
         return fail(TSG_ERR_ARG, "shape mismatch: handle has K=" + std::to_string(h->plan.K) + " N=" +
                                      std::to_string(h->plan.N) + ", call has K=" + std::to_string(K) +
@@ -557,7 +560,7 @@ int run_dev(tsg_tcsc *h, const void *dX, const float *db, const float *dalpha, f
     std::lock_guard<std::mutex> lk(h->mu);
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     HIP_TRY(hipStreamIsCapturing(s, &cap));
-    const Call c{dX, xtype, db, dalpha, dY, ldY, M, s, prelu, cap != hipStreamCaptureStatusNone};
+    const Call c{dX, xtype, db, dalpha, dY, ytype, ldY, M, s, prelu, cap != hipStreamCaptureStatusNone};
     CallPlan p = tsg::plan_call(h->plan, M);
     if (p.is_ell()) return run_ell(h, p, c);
     if (!p.is_jit()) return run_rx(h, p, c);
@@ -1296,6 +1299,22 @@ extern "C" int tcsc_hip_gemm_prelu_dev_x(tsg_tcsc *h, const void *dX, int xtype,
                                          void *stream)
 {
     return run_dev(h, dX, db, dalpha, dY, ldY, M, N, K, (hipStream_t)stream, true, xtype);
+}
+
+// Y of another element type (tsg_ytype): the same calls again, the type carried
+// to the epilogue of the kernel that stores Y (Call::ytype); TSG_Y_F32 is
+// tcsc_hip_gemm_dev_x
+extern "C" int tcsc_hip_gemm_dev_xy(tsg_tcsc *h, const void *dX, int xtype, const float *db, void *dY, int ytype,
+                                    int64_t ldY, int M, int N, int K, void *stream)
+{
+    return run_dev(h, dX, db, nullptr, dY, ldY, M, N, K, (hipStream_t)stream, false, xtype, ytype);
+}
+
+extern "C" int tcsc_hip_gemm_prelu_dev_xy(tsg_tcsc *h, const void *dX, int xtype, const float *db,
+                                          const float *dalpha, void *dY, int ytype, int64_t ldY, int M, int N, int K,
+                                          void *stream)
+{
+    return run_dev(h, dX, db, dalpha, dY, ldY, M, N, K, (hipStream_t)stream, true, xtype, ytype);
 }
 
 extern "C" int tcsc_hip_info(const tsg_tcsc *h, tsg_info *o)

@@ -43,6 +43,7 @@
 
 #include "tsg_internal.h"
 #include "tsg_xtype.h"
+#include "tsg_ytype.h"
 
 namespace tsg {
 
@@ -240,8 +241,8 @@ __device__ __forceinline__ void ell_stage(float *xs, const T *__restrict__ X, in
 template <typename T, int LG, int RPL, int WPG, int LA, bool PRELU>
 __global__ __launch_bounds__(WPG * 64) void tsg_tcsc_ell_kernel(
     const T *__restrict__ X, const uint4 *__restrict__ ent, const uint2 *__restrict__ tab,
-    const float *__restrict__ b, const float *__restrict__ alpha, float *__restrict__ Y, int64_t ldY, int M, int N,
-    int K, int C, int nch, int steps, int nsg, int xb, int zr)
+    const float *__restrict__ b, const float *__restrict__ alpha, float *__restrict__ Y, int64_t ldY, int ytype, int M,
+    int N, int K, int C, int nch, int steps, int nsg, int xb, int zr)
 {
     constexpr int MT = LG * RPL;                     // M rows of the tile
     constexpr int CPW = 64 / LG;                     // columns per wave
@@ -308,7 +309,10 @@ __global__ __launch_bounds__(WPG * 64) void tsg_tcsc_ell_kernel(
         if (m >= M) break;
         float v = y[r] + bn;                         // comp.h:63
         if (PRELU) v = (v > 0) ? v : an * v;         // comp_prelu.h:57-67
-        Y[(size_t)m * (size_t)ldY + n] = v;
+        if (ytype != kYF32)  // a 16-bit Y (uniform): rounded once, one 2-byte store (tsg_ytype.h)
+            ystore1(Y, ytype, (size_t)m * (size_t)ldY + n, v);
+        else
+            Y[(size_t)m * (size_t)ldY + n] = v;
     }
 }
 
@@ -354,8 +358,8 @@ struct PcShape {
 template <typename T, int MT, int E, bool PRELU>
 __global__ __launch_bounds__(64 * (MT + E / 8)) void tsg_tcsc_ell_pc_kernel(
     const T *__restrict__ X, const uint4 *__restrict__ ent, const uint2 *__restrict__ tab,
-    const float *__restrict__ b, const float *__restrict__ alpha, float *__restrict__ Y, int64_t ldY, int M, int N,
-    int K, int C, int nsg)
+    const float *__restrict__ b, const float *__restrict__ alpha, float *__restrict__ Y, int64_t ldY, int ytype, int M,
+    int N, int K, int C, int nsg)
 {
     using S = PcShape<MT, E>;
     static_assert(S::NT == 64 * (MT + E / 8), "launch bounds");
@@ -436,7 +440,10 @@ __global__ __launch_bounds__(64 * (MT + E / 8)) void tsg_tcsc_ell_pc_kernel(
         if (n >= N || m0 + r >= M) return;
         float v = y + b[n];                          // comp.h:63
         if (PRELU) v = (v > 0) ? v : alpha[n] * v;   // comp_prelu.h:57-67
-        Y[(size_t)(m0 + r) * (size_t)ldY + n] = v;
+        if (ytype != kYF32)  // a 16-bit Y (uniform): rounded once, one 2-byte store (tsg_ytype.h)
+            ystore1(Y, ytype, (size_t)(m0 + r) * (size_t)ldY + n, v);
+        else
+            Y[(size_t)(m0 + r) * (size_t)ldY + n] = v;
     } else {
         const uint32_t base = (uint32_t)(uintptr_t)(lds_f *)xs;
         // A block's 8 entries, all MT rows each (one LDS read per entry), are
@@ -533,7 +540,7 @@ namespace {
 
 template <typename T, int LG, int RPL, int WPG, int LA>
 int launch_ell_la(const T *X, const uint4 *ent, const uint2 *tab, const float *b, const float *alpha, float *Y,
-                  int64_t ldY, int M, int N, int K, int C, int nch, int xb, int zr, int prelu, hipStream_t s)
+                  int64_t ldY, int ytype, int M, int N, int K, int C, int nch, int xb, int zr, int prelu, hipStream_t s)
 {
     constexpr int MT = LG * RPL, CPW = 64 / LG;
     const int nsg = (N + WPG * CPW - 1) / (WPG * CPW);
@@ -543,10 +550,10 @@ int launch_ell_la(const T *X, const uint4 *ent, const uint2 *tab, const float *b
     const dim3 grid((unsigned)(nsg * mtiles)), block(WPG * 64);
     if (prelu)
         hipLaunchKernelGGL((tsg_tcsc_ell_kernel<T, LG, RPL, WPG, LA, true>), grid, block, lds, s, X, ent, tab, b, alpha,
-                           Y, ldY, M, N, K, C, nch, steps, nsg, xb, zr);
+                           Y, ldY, ytype, M, N, K, C, nch, steps, nsg, xb, zr);
     else
         hipLaunchKernelGGL((tsg_tcsc_ell_kernel<T, LG, RPL, WPG, LA, false>), grid, block, lds, s, X, ent, tab, b, alpha,
-                           Y, ldY, M, N, K, C, nch, steps, nsg, xb, zr);
+                           Y, ldY, ytype, M, N, K, C, nch, steps, nsg, xb, zr);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -563,11 +570,11 @@ int pick_la()
 
 template <typename T, int LG, int RPL, int WPG>
 int launch_ell_t(const T *X, const uint4 *ent, const uint2 *tab, const float *b, const float *alpha, float *Y,
-                 int64_t ldY, int M, int N, int K, int C, int nch, int xb, int zr, int prelu, hipStream_t s)
+                 int64_t ldY, int ytype, int M, int N, int K, int C, int nch, int xb, int zr, int prelu, hipStream_t s)
 {
     if (pick_la() == 2)
-        return launch_ell_la<T, LG, RPL, WPG, 2>(X, ent, tab, b, alpha, Y, ldY, M, N, K, C, nch, xb, zr, prelu, s);
-    return launch_ell_la<T, LG, RPL, WPG, 1>(X, ent, tab, b, alpha, Y, ldY, M, N, K, C, nch, xb, zr, prelu, s);
+        return launch_ell_la<T, LG, RPL, WPG, 2>(X, ent, tab, b, alpha, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
+    return launch_ell_la<T, LG, RPL, WPG, 1>(X, ent, tab, b, alpha, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
 }
 
 }  // namespace
@@ -589,7 +596,7 @@ constexpr int64_t kEllWideWgs = 224;  // 7/8 of the CUs
 
 template <typename T, int LG, int RPL>
 int launch_lg(const T *X, const uint4 *e, const uint2 *t, const float *b, const float *alpha, float *Y,
-              int64_t ldY, int M, int N, int K, int C, int nch, int xb, int zr, int prelu, hipStream_t s)
+              int64_t ldY, int ytype, int M, int N, int K, int C, int nch, int xb, int zr, int prelu, hipStream_t s)
 {
     constexpr int MT = LG * RPL, CPW = 64 / LG;
     const int64_t waves = (int64_t)((N + CPW - 1) / CPW) * ((M + MT - 1) / MT);
@@ -598,11 +605,11 @@ int launch_lg(const T *X, const uint4 *e, const uint2 *t, const float *b, const 
         const char *v = knob_value("TSG_ELL_WPG");
         return v ? atoi(v) : 0;
     }();
-    if (env_wpg == 4) return launch_ell_t<T, LG, RPL, 4>(X, e, t, b, alpha, Y, ldY, M, N, K, C, nch, xb, zr, prelu, s);
+    if (env_wpg == 4) return launch_ell_t<T, LG, RPL, 4>(X, e, t, b, alpha, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
     if constexpr (RPL <= 2) {
-        if (env_wpg == 8) return launch_ell_t<T, LG, RPL, 8>(X, e, t, b, alpha, Y, ldY, M, N, K, C, nch, xb, zr, prelu, s);
+        if (env_wpg == 8) return launch_ell_t<T, LG, RPL, 8>(X, e, t, b, alpha, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
         if (env_wpg == 16)
-            return launch_ell_t<T, LG, RPL, 16>(X, e, t, b, alpha, Y, ldY, M, N, K, C, nch, xb, zr, prelu, s);
+            return launch_ell_t<T, LG, RPL, 16>(X, e, t, b, alpha, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
     }
     if constexpr (RPL <= 2) {
         auto one_round = [&](int64_t wpg) {  // >= 7/8 of the CUs busy, no second round
@@ -610,14 +617,14 @@ int launch_lg(const T *X, const uint4 *e, const uint2 *t, const float *b, const 
             return wgs >= kEllWideWgs && wgs <= 256 * per_cu;
         };
         if (one_round(16))
-            return launch_ell_t<T, LG, RPL, 16>(X, e, t, b, alpha, Y, ldY, M, N, K, C, nch, xb, zr, prelu, s);
-        if (one_round(8)) return launch_ell_t<T, LG, RPL, 8>(X, e, t, b, alpha, Y, ldY, M, N, K, C, nch, xb, zr, prelu, s);
+            return launch_ell_t<T, LG, RPL, 16>(X, e, t, b, alpha, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
+        if (one_round(8)) return launch_ell_t<T, LG, RPL, 8>(X, e, t, b, alpha, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
         if (waves > 256 * per_cu * 8)
-            return launch_ell_t<T, LG, RPL, 16>(X, e, t, b, alpha, Y, ldY, M, N, K, C, nch, xb, zr, prelu, s);
+            return launch_ell_t<T, LG, RPL, 16>(X, e, t, b, alpha, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
         if (waves > 256 * per_cu * 4)
-            return launch_ell_t<T, LG, RPL, 8>(X, e, t, b, alpha, Y, ldY, M, N, K, C, nch, xb, zr, prelu, s);
+            return launch_ell_t<T, LG, RPL, 8>(X, e, t, b, alpha, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
     }
-    return launch_ell_t<T, LG, RPL, 4>(X, e, t, b, alpha, Y, ldY, M, N, K, C, nch, xb, zr, prelu, s);
+    return launch_ell_t<T, LG, RPL, 4>(X, e, t, b, alpha, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
 }
 
 // lanes per column of an M tile: the default, or TSG_ELL_LG (diagnostic sweeps)
@@ -638,7 +645,7 @@ constexpr size_t pc_lds(int C)
 
 template <typename T, int MT, int E>
 int launch_pc_t(const T *X, const uint4 *ent, const uint2 *tab, const float *b, const float *alpha, float *Y,
-                int64_t ldY, int M, int N, int K, int C, int prelu, hipStream_t s)
+                int64_t ldY, int ytype, int M, int N, int K, int C, int prelu, hipStream_t s)
 {
     using S = PcShape<MT, E>;
     const int nsg = (N + 63) / 64;
@@ -646,10 +653,10 @@ int launch_pc_t(const T *X, const uint4 *ent, const uint2 *tab, const float *b, 
     const size_t lds = pc_lds<MT, E>(C);
     const dim3 grid((unsigned)(nsg * mtiles)), block(S::NT);
     if (prelu)
-        hipLaunchKernelGGL((tsg_tcsc_ell_pc_kernel<T, MT, E, true>), grid, block, lds, s, X, ent, tab, b, alpha, Y, ldY, M,
+        hipLaunchKernelGGL((tsg_tcsc_ell_pc_kernel<T, MT, E, true>), grid, block, lds, s, X, ent, tab, b, alpha, Y, ldY, ytype, M,
                            N, K, C, nsg);
     else
-        hipLaunchKernelGGL((tsg_tcsc_ell_pc_kernel<T, MT, E, false>), grid, block, lds, s, X, ent, tab, b, alpha, Y, ldY,
+        hipLaunchKernelGGL((tsg_tcsc_ell_pc_kernel<T, MT, E, false>), grid, block, lds, s, X, ent, tab, b, alpha, Y, ldY, ytype,
                            M, N, K, C, nsg);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
@@ -693,9 +700,10 @@ size_t ell_pc_lds_bytes(int variant, int C)
 }
 
 int launch_tcsc_ell_pc(int variant, const void *X, int xtype, const uint32_t *ent, const uint32_t *tab, const float *b,
-                       const float *alpha, float *Y, int64_t ldY, int M, int N, int K, int C, int nch, int prelu,
-                       void *stream)
+                       const float *alpha, void *Yv, int ytype, int64_t ldY, int M, int N, int K, int C, int nch,
+                       int prelu, void *stream)
 {
+    float *Y = static_cast<float *>(Yv);  // elements of ytype; the kernels' epilogue casts (tsg_ytype.h)
     // one stream per column, X chunk + ring within a workgroup's LDS
     if (nch != 1 || ell_pc_lds_bytes(variant, C) == 0 || ell_pc_lds_bytes(variant, C) > kLdsBytes) return -2;
     hipStream_t s = (hipStream_t)stream;
@@ -705,9 +713,9 @@ int launch_tcsc_ell_pc(int variant, const void *X, int xtype, const uint32_t *en
     return with_xtype(X, xtype, [&](auto *x) {
         using T = std::remove_cv_t<std::remove_pointer_t<decltype(x)>>;
         switch (phase) {
-        case 16: return launch_pc_t<T, 1, 16>(x, e, t, b, alpha, Y, ldY, M, N, K, C, prelu, s);
-        case 64: return launch_pc_t<T, 1, 64>(x, e, t, b, alpha, Y, ldY, M, N, K, C, prelu, s);
-        default: return launch_pc_t<T, 1, 32>(x, e, t, b, alpha, Y, ldY, M, N, K, C, prelu, s);  // 1 consumer, 4 producers
+        case 16: return launch_pc_t<T, 1, 16>(x, e, t, b, alpha, Y, ldY, ytype, M, N, K, C, prelu, s);
+        case 64: return launch_pc_t<T, 1, 64>(x, e, t, b, alpha, Y, ldY, ytype, M, N, K, C, prelu, s);
+        default: return launch_pc_t<T, 1, 32>(x, e, t, b, alpha, Y, ldY, ytype, M, N, K, C, prelu, s);  // 1 consumer, 4 producers
         }
     });
 }
@@ -716,13 +724,13 @@ namespace {
 
 template <typename T>
 int launch_ell_variant(int variant, const T *X, const uint4 *e, const uint2 *t, const float *b, const float *alpha,
-                       float *Y, int64_t ldY, int M, int N, int K, int C, int nch, int xb, int zr, int prelu,
+                       float *Y, int64_t ldY, int ytype, int M, int N, int K, int C, int nch, int xb, int zr, int prelu,
                        hipStream_t s)
 {
 #define TSG_ELL_LG(lg, rpl) \
-    case lg: return launch_lg<T, lg, rpl>(X, e, t, b, alpha, Y, ldY, M, N, K, C, nch, xb, zr, prelu, s)
+    case lg: return launch_lg<T, lg, rpl>(X, e, t, b, alpha, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s)
     switch (variant) {
-    case 0: return launch_ell_t<T, 1, 1, 1>(X, e, t, b, alpha, Y, ldY, M, N, K, C, nch, xb, zr, prelu, s);  // MT = 1
+    case 0: return launch_ell_t<T, 1, 1, 1>(X, e, t, b, alpha, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);  // MT = 1
     case 1:                                                                                   // MT = 4
         switch (pick_lg(4)) {
             TSG_ELL_LG(4, 1);
@@ -755,9 +763,10 @@ int launch_ell_variant(int variant, const T *X, const uint4 *e, const uint2 *t, 
 }  // namespace
 
 int launch_tcsc_ell(int variant, const void *X, int xtype, const uint32_t *ent, const uint32_t *tab, const float *b,
-                    const float *alpha, float *Y, int64_t ldY, int M, int N, int K, int C, int nch, int xb, int zr,
-                    int prelu, void *stream)
+                    const float *alpha, void *Yv, int ytype, int64_t ldY, int M, int N, int K, int C, int nch, int xb,
+                    int zr, int prelu, void *stream)
 {
+    float *Y = static_cast<float *>(Yv);  // elements of ytype; the kernels' epilogue casts (tsg_ytype.h)
     // the second X^T copy and the bank-window schedule serve the 8-row tile's
     // 4-lane columns only (tsg_host.cpp build_ell_image)
     if ((xb || zr != 1) && (variant != 2 || pick_lg(4) != 4)) return -2;
@@ -765,7 +774,7 @@ int launch_tcsc_ell(int variant, const void *X, int xtype, const uint32_t *ent, 
     const uint4 *e = reinterpret_cast<const uint4 *>(ent);
     const uint2 *t = reinterpret_cast<const uint2 *>(tab);
     return with_xtype(X, xtype, [&](auto *x) {
-        return launch_ell_variant(variant, x, e, t, b, alpha, Y, ldY, M, N, K, C, nch, xb, zr, prelu, s);
+        return launch_ell_variant(variant, x, e, t, b, alpha, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
     });
 }
 

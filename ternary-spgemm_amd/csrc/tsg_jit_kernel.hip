@@ -46,6 +46,7 @@
 #include <cstdint>
 
 #include "tsg_jit_map.h"
+#include "tsg_ytype.h"
 
 namespace {
 
@@ -174,13 +175,15 @@ extern "C" __global__ __launch_bounds__(64) void tsg_jit_probe(uint32_t *__restr
 // code object's dispatcher takes the argument list that ends in ldY.  A
 // template without it is refused at load.
 extern "C" __global__ __launch_bounds__(64) void tsg_jit_args_ldy() {}
+// The same for the argument after it, ytype (looked up after the first)
+extern "C" __global__ __launch_bounds__(64) void tsg_jit_args_ytype() {}
 
 // (the half ring: two workgroups per CU, so at most 256 VGPRs -- two waves per SIMD)
 extern "C" __global__ __launch_bounds__(kJThreads, kJHalf ? 2 : 1) void TSG_JIT_KERNEL_NAME(
     const float *__restrict__ XT, int Mp, const uint32_t *__restrict__ wcode,
     const float *__restrict__ b, const float *__restrict__ alpha, float *__restrict__ Y, int M, int N,
     int nch, int mtiles, int ntiles, int prelu, uint32_t *__restrict__ status, int gn, int gm,
-    int tmask, int xrow, int lastadj, int xtouch, int tnear, int64_t ldY)
+    int tmask, int xrow, int lastadj, int xtouch, int tnear, int64_t ldY, int ytype)
 {
     __shared__ __attribute__((aligned(16))) char lds[kJRing * kJBufBytes];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -390,6 +393,29 @@ extern "C" __global__ __launch_bounds__(kJThreads, kJHalf ? 2 : 1) void TSG_JIT_
 
     if (ncol0 >= N) return;
     if (kJPair && (lane >> 5) != rhalf) return;  // the pair's other wave holds these rows
+    if (__builtin_expect(ytype != tsg::kYF32, 0)) {  // (out of line: the fp32 path keeps its layout)
+        // a 16-bit Y (uniform): the same fp32 value, rounded once and stored
+        // 8 columns at a time (tsg_ytype.h); ldY counts 16-bit elements
+#pragma unroll
+        for (int r = 0; r < kJRowsPerLane; r++) {
+            const int m = m0 + kJRowsPerLane * lane + r;
+            if (m >= M) continue;
+            // this branch's own copies of what the fp32 stores below use too:
+            // the compiler would otherwise compute every column's bias address
+            // once for both branches, ahead of them, and keep it in scalar
+            // registers the fp32 path then has to spill around
+            int nc0 = ncol0;
+            const float *b16 = b, *alpha16 = alpha;
+            asm volatile("" : "+s"(nc0), "+s"(b16), "+s"(alpha16));
+            tsg::ystore_seg<kJNW>(Y, ytype, (size_t)m * (size_t)ldY + nc0, N - nc0, [&](int c) {
+                const int n = nc0 + c < N ? nc0 + c : N - 1;
+                float y = acc_of(c, r) + b16[n];               // comp.h:63
+                if (prelu) y = (y > 0) ? y : alpha16[n] * y;   // comp_prelu.h:57-67
+                return y;
+            });
+        }
+        return;
+    }
 #pragma unroll
     for (int r = 0; r < kJRowsPerLane; r++) {
         const int m = m0 + kJRowsPerLane * lane + r;

@@ -50,10 +50,13 @@ EXPORTED_SYMBOLS = (
     "tsg_jit_codegen64", "tsg_jit_codegen64h", "tcsc_hip_call_launches",
     "tcsc_hip_gemm_dev_ld", "tcsc_hip_gemm_prelu_dev_ld",
     "tcsc_hip_gemm_dev_x", "tcsc_hip_gemm_prelu_dev_x",
+    "tcsc_hip_gemm_dev_xy", "tcsc_hip_gemm_prelu_dev_xy",
 )
 
 # enum tsg_xtype (include/ternary_spgemm.h): element type of X on the _x calls
 TSG_X_F32, TSG_X_F16, TSG_X_BF16, TSG_X_I8 = 0, 1, 2, 3
+# enum tsg_ytype: element type of Y on the _xy calls
+TSG_Y_F32, TSG_Y_F16, TSG_Y_BF16 = 0, 1, 2
 
 
 class TSGError(RuntimeError):
@@ -107,6 +110,9 @@ def lib() -> C.CDLL:
     L.tcsc_hip_gemm_prelu_dev_ld.argtypes = [H, vp, vp, vp, vp, C.c_int64, C.c_int, C.c_int, C.c_int, vp]
     L.tcsc_hip_gemm_dev_x.argtypes = [H, vp, C.c_int, vp, vp, C.c_int64, C.c_int, C.c_int, C.c_int, vp]
     L.tcsc_hip_gemm_prelu_dev_x.argtypes = [H, vp, C.c_int, vp, vp, vp, C.c_int64, C.c_int, C.c_int, C.c_int, vp]
+    L.tcsc_hip_gemm_dev_xy.argtypes = [H, vp, C.c_int, vp, vp, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, vp]
+    L.tcsc_hip_gemm_prelu_dev_xy.argtypes = [H, vp, C.c_int, vp, vp, vp, C.c_int, C.c_int64, C.c_int, C.c_int,
+                                             C.c_int, vp]
     L.tcsc_hip_reserve.argtypes = [H, C.c_int]
     L.tcsc_hip_info.argtypes = [H, C.POINTER(tsg_info)]
     L.tcsc_hip_to_dense.argtypes = [H, vp, C.c_int, C.c_int]
@@ -639,40 +645,78 @@ class TCSCDevice:
         gemm_torch(X.float(), b) bit for bit.  b and alpha are float32; Y is
         None (a new contiguous [M, N] float32 tensor) or a strided output as in
         gemm_torch_into.  Returns Y."""
+        return self._torch_xy("gemm_torch_x", X, b, Y, alpha, None, narrow_y=False)
+
+    def gemm_dev_xy(self, dX: int, xtype: int, db: int, dY: int, ytype: int, M: int, stream: int = 0,
+                    dalpha: Optional[int] = None, ldY: Optional[int] = None) -> None:
+        """gemm_dev_x with Y in the element type ytype names (TSG_Y_F32 / _F16 /
+        _BF16; tcsc_hip_gemm_dev_xy): the fp32 result rounded once, to nearest
+        even, right before the store.  ldY counts elements of that type; None =
+        the dense [M, N] block.  b and alpha stay fp32."""
+        ld = self.N if ldY is None else int(ldY)
+        if dalpha is None:
+            _check(lib().tcsc_hip_gemm_dev_xy(self._h, dX, int(xtype), db, dY, int(ytype), ld, M, self.N, self.K,
+                                              stream or None), "tcsc_hip_gemm_dev_xy")
+        else:
+            _check(lib().tcsc_hip_gemm_prelu_dev_xy(self._h, dX, int(xtype), db, dalpha, dY, int(ytype), ld, M,
+                                                    self.N, self.K, stream or None), "tcsc_hip_gemm_prelu_dev_xy")
+
+    def gemm_torch_xy(self, X, b, Y=None, alpha=None, out_dtype=None):
+        """gemm_torch_x with a Y of any supported element type: X as there; Y
+        is None -- a new contiguous [M, N] tensor of out_dtype (float32 by
+        default) -- or a float32, float16 or bfloat16 [M, N] tensor with
+        contiguous, non-overlapping rows (out_dtype, when also given, must be
+        its dtype).  The result is gemm_torch_x(X, b).to(dtype) bit for bit:
+        the fp32 value rounded once, in the kernel's epilogue.  Returns Y."""
+        return self._torch_xy("gemm_torch_xy", X, b, Y, alpha, out_dtype, narrow_y=True)
+
+    def _torch_xy(self, where, X, b, Y, alpha, out_dtype, narrow_y):
         import torch
         dev = torch.device("cuda", self.device)
+        ytypes = {torch.float32: TSG_Y_F32}
+        if narrow_y:
+            ytypes.update({torch.float16: TSG_Y_F16, torch.bfloat16: TSG_Y_BF16})
+        ynames = "float32, float16 or bfloat16" if narrow_y else "float32"
         xtypes = {torch.float32: TSG_X_F32, torch.float16: TSG_X_F16, torch.bfloat16: TSG_X_BF16,
                   torch.int8: TSG_X_I8}
         if not (isinstance(X, torch.Tensor) and X.dim() == 2 and X.shape[1] == self.K):
-            raise TSGError(1, "gemm_torch_x", f"X must be a [M, {self.K}] tensor, got "
+            raise TSGError(1, where, f"X must be a [M, {self.K}] tensor, got "
                                               f"{tuple(X.shape) if isinstance(X, torch.Tensor) else type(X)}")
         M = X.shape[0]
         if X.dtype not in xtypes or X.device != dev or not X.is_contiguous():
-            raise TSGError(1, "gemm_torch_x", f"X must be a contiguous float32, float16, bfloat16 or int8 "
+            raise TSGError(1, where, f"X must be a contiguous float32, float16, bfloat16 or int8 "
                                               f"{[M, self.K]} tensor on {dev}, got {X.dtype} {list(X.shape)} on "
                                               f"{X.device}{'' if X.is_contiguous() else ' (non-contiguous)'}")
         for name, t, shape in (("b", b, (self.N,)), ("alpha", alpha, (self.N,))):
             if t is None:
                 continue
             if t.dtype != torch.float32 or t.device != dev or not t.is_contiguous() or tuple(t.shape) != shape:
-                raise TSGError(1, "gemm_torch_x", f"{name} must be a contiguous float32 {list(shape)} tensor on "
+                raise TSGError(1, where, f"{name} must be a contiguous float32 {list(shape)} tensor on "
                                                   f"{dev}, got {t.dtype} {list(t.shape)} on {t.device}"
                                                   f"{'' if t.is_contiguous() else ' (non-contiguous)'}")
+        if out_dtype is not None and out_dtype not in ytypes:
+            raise TSGError(1, where, f"out_dtype must be {ynames}, got {out_dtype}")
         if Y is None:
-            Y = torch.empty((M, self.N), dtype=torch.float32, device=dev)
-        if not isinstance(Y, torch.Tensor) or Y.dtype != torch.float32 or Y.device != dev or \
+            Y = torch.empty((M, self.N), dtype=out_dtype or torch.float32, device=dev)
+        if not isinstance(Y, torch.Tensor) or Y.dtype not in ytypes or Y.device != dev or \
                 tuple(Y.shape) != (M, self.N):
             got = (Y.dtype, list(Y.shape), Y.device) if isinstance(Y, torch.Tensor) else type(Y)
-            raise TSGError(1, "gemm_torch_x", f"Y must be a float32 [{M}, {self.N}] tensor on {dev}, got {got}")
+            raise TSGError(1, where, f"Y must be a {ynames} [{M}, {self.N}] tensor on {dev}, got {got}")
+        if out_dtype is not None and Y.dtype != out_dtype:
+            raise TSGError(1, where, f"Y is {Y.dtype}, out_dtype is {out_dtype}: they must agree")
         if self.N > 1 and Y.stride(1) != 1:
-            raise TSGError(1, "gemm_torch_x", f"Y's rows must be contiguous (stride(1) == 1), got {Y.stride()}")
+            raise TSGError(1, where, f"Y's rows must be contiguous (stride(1) == 1), got {Y.stride()}")
         # one row has no next row: any row stride describes it
         ldY = self.N if M <= 1 else Y.stride(0)
         if ldY < self.N:
-            raise TSGError(1, "gemm_torch_x", f"Y's rows overlap: stride(0) = {ldY} < N = {self.N}")
+            raise TSGError(1, where, f"Y's rows overlap: stride(0) = {ldY} < N = {self.N}")
         stream = torch.cuda.current_stream(dev).cuda_stream
-        self.gemm_dev_x(X.data_ptr(), xtypes[X.dtype], b.data_ptr(), Y.data_ptr(), M, stream,
-                        None if alpha is None else alpha.data_ptr(), ldY=ldY)
+        dalpha = None if alpha is None else alpha.data_ptr()
+        if narrow_y:
+            self.gemm_dev_xy(X.data_ptr(), xtypes[X.dtype], b.data_ptr(), Y.data_ptr(), ytypes[Y.dtype], M, stream,
+                             dalpha, ldY=ldY)
+        else:
+            self.gemm_dev_x(X.data_ptr(), xtypes[X.dtype], b.data_ptr(), Y.data_ptr(), M, stream, dalpha, ldY=ldY)
         return Y
 
     def gemm_torch(self, X, b, Y=None, alpha=None):
