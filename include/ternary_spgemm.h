@@ -244,6 +244,58 @@ int tcsc_hip_gemm_prelu_dev_xy(tsg_tcsc *h, const void *dX, int xtype, const flo
                                const float *dalpha, void *dY, int ytype, int64_t ldY, int M, int N,
                                int K, void *stream);
 
+/* The same two calls once more with a per-row and a per-column scale in the
+ * epilogue.  A ternary W comes with a weight scale (W ~ gamma * T, per tensor
+ * or per output column) and int8 activations with a per-row (per-token)
+ * dequantisation scale; the layer needs
+ *
+ *   Y[m, n] = chain(m, n) * drow_scale[m] * dcol_scale[n] + db[n]
+ *
+ * from the one call, without a zero b, an fp32 Y and a second pass over Y --
+ * and with int8 X the unscaled chains (integers up to 127 * nnz(column)) would
+ * overflow an fp16 Y from 65520 on.  drow_scale is float[M], dcol_scale is
+ * float[N], both device memory that needs only 4-byte alignment (slices are
+ * fine); either may be NULL.
+ *
+ * Order and rounding.  All arithmetic is fp32, one rounding per operation, no
+ * fused multiply-add anywhere:
+ *
+ *   t = chain                  exactly the value tcsc_hip_gemm_dev_x adds b to
+ *                              (a blocked handle: after its last block)
+ *   if (drow_scale) t = t * drow_scale[m]        rounded
+ *   if (dcol_scale) t = t * dcol_scale[n]        rounded
+ *   y = t + db[n]                                rounded, never contracted with
+ *                                                the multiply before it
+ *   PReLU as on the other calls, then the one rounding to ytype as on _xy.
+ *
+ * Special values.  A scale may be any fp32 value -- 0, negative, subnormal,
+ * inf, NaN: Y is the IEEE result of the operations above (a NaN's payload is
+ * not promised, as elsewhere in this library).
+ * NULL scales.  A NULL scale means its multiply is not performed (not a
+ * multiply by 1).  With both NULL the call is tcsc_hip_gemm_dev_xy itself: the
+ * same path, bit for bit.
+ * As on _xy: the meaning of ldY (elements of the Y type, >= N), dY's alignment
+ * and the guarantee that only [m * ldY, m * ldY + N) of each row is written,
+ * the 16-bit neighbour in a shared dword included; stream semantics,
+ * tcsc_hip_reserve and graph capture; the kernel and image an M picks and the
+ * direct-X path of the 64-row image; the work buffer.  The scales add no
+ * launch, no allocation and no synchronisation: they are two more pointers of
+ * the kernel that stores Y.
+ * Isolation.  The isolation paragraph above extends to the scales: no result
+ * depends on memory outside [drow_scale, drow_scale + M) and [dcol_scale,
+ * dcol_scale + N), and the scales are never written.
+ * Errors.  A bad xtype, ytype or ldY and a null handle are TSG_ERR_ARG with a
+ * message, nothing enqueued, as on _xy.
+ * Out of scope: a NULL db (pass zeros); the host-pointer calls, which stay
+ * fp32 and unscaled; the plugin header (tcsc_hip_plugin.hpp).  Extension: no
+ * reference counterpart. */
+int tcsc_hip_gemm_dev_scaled(tsg_tcsc *h, const void *dX, int xtype, const float *drow_scale,
+                             const float *dcol_scale, const float *db, void *dY, int ytype, int64_t ldY,
+                             int M, int N, int K, void *stream);
+int tcsc_hip_gemm_prelu_dev_scaled(tsg_tcsc *h, const void *dX, int xtype, const float *drow_scale,
+                                   const float *dcol_scale, const float *db, const float *dalpha, void *dY,
+                                   int ytype, int64_t ldY, int M, int N, int K, void *stream);
+
 /* Pre-allocates the per-handle work buffer for row counts up to max_M and, on
  * the weight-compiled kernel, compiles every code image a call with M <= max_M
  * rows runs (and the small-M images), so no later such call allocates or

@@ -23,6 +23,7 @@
 #include <type_traits>
 
 #include "tsg_internal.h"
+#include "tsg_scale.h"
 #include "tsg_xtype.h"
 #include "tsg_ytype.h"
 
@@ -287,7 +288,8 @@ template <bool PRELU>
 __global__ __launch_bounds__(kRxWaves * 64, 8 / kRxWaves) void tsg_tcsc_rx_kernel(
     const float *__restrict__ XT, int Mp, const uint32_t *__restrict__ wstart,
     const uint32_t *__restrict__ ent, const float *__restrict__ b, const float *__restrict__ alpha,
-    float *__restrict__ Y, int64_t ldY, int ytype, int M, int N, int nch, int mtiles, int ntiles)
+    float *__restrict__ Y, int64_t ldY, int ytype, int M, int N, int nch, int mtiles, int ntiles,
+    const float *__restrict__ rs, const float *__restrict__ cs)
 {
     __shared__ __attribute__((aligned(16))) char lds[kRxLdsBytes];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -329,6 +331,30 @@ __global__ __launch_bounds__(kRxWaves * 64, 8 / kRxWaves) void tsg_tcsc_rx_kerne
         __syncthreads();
     }
     if (ncol0 >= N) return;
+    if ((rs != nullptr) | (cs != nullptr)) {
+        // a scaled call (uniform; tsg_scale.h): ((chain * rs[m]) * cs[n]) + b[n],
+        // three roundings, then the PReLU and the store of any Y type
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            const int m = m0 + 4 * lane + r;
+            if (m >= M) continue;
+            // this branch's own copies, fenced like the 16-bit branch's
+            int nc0 = ncol0;
+            const float *bs = b, *alphas = alpha, *rss = rs, *css = cs;
+            asm volatile("" : "+s"(nc0), "+s"(bs), "+s"(alphas), "+s"(rss), "+s"(css));
+            const bool has_rs = rss != nullptr, has_cs = css != nullptr;
+            const float rm = has_rs ? rss[m] : 0.0f;
+            ystore_seg_any<kRxNW>(Y, ytype, (size_t)m * (size_t)ldY + nc0, N - nc0, [&](int c) {
+                const int n = nc0 + c < N ? nc0 + c : N - 1;
+                const float acc = c < 8 ? a0[4 * (c & 7) + r] : c < 16 ? a1[4 * (c & 7) + r]
+                                 : c < 24 ? a2[4 * (c & 7) + r] : a3[4 * (c & 7) + r];
+                float y = scale_bias(acc, has_rs, rm, has_cs, has_cs ? css[n] : 0.0f, bs[n]);
+                if (PRELU) y = (y > 0) ? y : alphas[n] * y;  // comp_prelu.h:57-67
+                return y;
+            });
+        }
+        return;
+    }
     if (ytype != kYF32) {
         // a 16-bit Y (uniform): the same fp32 value, rounded once and stored
         // 8 columns at a time (tsg_ytype.h); ldY counts 16-bit elements
@@ -454,18 +480,18 @@ int launch_transpose_quads(const void *X, int xtype, float *XQ, int M, int K, in
 }
 
 int launch_tcsc_rx(const float *XT, int Mp, const uint32_t *wstart, const uint32_t *ent,
-                   const float *b, const float *alpha, void *Y, int ytype, int64_t ldY, int M, int N, int Npad,
-                   int nch, int prelu, void *stream)
+                   const float *b, const float *alpha, const float *rs, const float *cs, void *Y, int ytype,
+                   int64_t ldY, int M, int N, int Npad, int nch, int prelu, void *stream)
 {
     hipStream_t s = (hipStream_t)stream;
     const int mtiles = Mp / kRxTileM, ntiles = Npad / kRxTileCols;
     const dim3 grid((unsigned)(mtiles * ntiles)), block(kRxWaves * kLanes);
     if (prelu)
         hipLaunchKernelGGL((tsg_tcsc_rx_kernel<true>), grid, block, 0, s, XT, Mp, wstart, ent, b, alpha,
-                           static_cast<float *>(Y), ldY, ytype, M, N, nch, mtiles, ntiles);
+                           static_cast<float *>(Y), ldY, ytype, M, N, nch, mtiles, ntiles, rs, cs);
     else
         hipLaunchKernelGGL((tsg_tcsc_rx_kernel<false>), grid, block, 0, s, XT, Mp, wstart, ent, b, alpha,
-                           static_cast<float *>(Y), ldY, ytype, M, N, nch, mtiles, ntiles);
+                           static_cast<float *>(Y), ldY, ytype, M, N, nch, mtiles, ntiles, rs, cs);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

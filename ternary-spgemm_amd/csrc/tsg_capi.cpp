@@ -400,6 +400,7 @@ struct Call {
     const void *dX;  // M x K row-major elements of xtype (tsg::XType)
     int xtype;
     const float *db, *dalpha;
+    const float *drs, *dcs;  // the epilogue scales, float[M] and float[N] (either may be null)
     void *dY;     // elements of ytype (tsg::YType)
     int ytype;
     int64_t ldY;  // elements of ytype from one Y row to the next (>= N)
@@ -449,9 +450,9 @@ int run_ell(tsg_tcsc *h, const CallPlan &p, const Call &c)
     const tsg_tcsc::EllVariant &e = h->ell[p.ell];
     const int N = h->plan.N, K = h->plan.K;
     const int lrc = p.kernel == Kernel::kEllPc
-                        ? tsg::launch_tcsc_ell_pc(p.ell, c.dX, c.xtype, e.d_ent, e.d_tab, c.db, c.dalpha, c.dY, c.ytype,
+                        ? tsg::launch_tcsc_ell_pc(p.ell, c.dX, c.xtype, e.d_ent, e.d_tab, c.db, c.dalpha, c.drs, c.dcs, c.dY, c.ytype,
                                                   c.ldY,                                                  c.M, N, K, e.img.C, e.img.nch, c.prelu ? 1 : 0, c.s)
-                        : tsg::launch_tcsc_ell(p.ell, c.dX, c.xtype, e.d_ent, e.d_tab, c.db, c.dalpha, c.dY, c.ytype, c.ldY,
+                        : tsg::launch_tcsc_ell(p.ell, c.dX, c.xtype, e.d_ent, e.d_tab, c.db, c.dalpha, c.drs, c.dcs, c.dY, c.ytype, c.ldY,
                                                c.M,                                               N, K, e.img.C, e.img.nch, e.img.xb, e.img.zr, c.prelu ? 1 : 0, c.s);
     if (lrc != 0)
         return fail(TSG_ERR_HIP, std::string("small-M kernel launch: ") + hipGetErrorString(hipGetLastError()));
@@ -474,7 +475,7 @@ int run_rx(tsg_tcsc *h, const CallPlan &p, const Call &c)
     int slot;
     rc = timing_begin(h, c.capturing, c.s, slot);
     if (rc) return rc;
-    if (tsg::launch_tcsc_rx(h->d_work, d.Mp, h->d_seg, h->d_ent, c.db, c.dalpha, c.dY, c.ytype, c.ldY, c.M, N,
+    if (tsg::launch_tcsc_rx(h->d_work, d.Mp, h->d_seg, h->d_ent, c.db, c.dalpha, c.drs, c.dcs, c.dY, c.ytype, c.ldY, c.M, N,
                             h->rimg.Npad, h->rimg.nch, c.prelu ? 1 : 0, c.s) != 0)
         return fail(TSG_ERR_HIP, std::string("tcsc launch: ") + hipGetErrorString(hipGetLastError()));
     rc = timing_end(h, slot, c.s);
@@ -526,7 +527,7 @@ int run_jit(tsg_tcsc *h, const CallPlan &p, const tsg_tcsc::JitVariant &jv, cons
     rc = timing_begin(h, c.capturing, c.s, slot);
     if (rc) return rc;
     if (tsg::launch_tcsc_jit(jv.mod, direct ? static_cast<const float *>(c.dX) : h->d_work, d.Mp, jv.d_wcode, c.db,
-                             c.dalpha, c.dY, c.ytype, c.ldY, c.M, N,
+                             c.dalpha, c.drs, c.dcs, c.dY, c.ytype, c.ldY, c.M, N,
                              jv.Npad, jv.nch, c.prelu ? 1 : 0, h->d_status, jv.nw * jv.waves, waves, p.gn, p.gm, p.tmask,
                              c.s, p.tile_m, direct ? K : 0, lastadj, p.xtouch, p.tnear) != 0)
         return fail(TSG_ERR_HIP, std::string("tcsc launch: ") + hipGetErrorString(hipGetLastError()));
@@ -536,7 +537,8 @@ int run_jit(tsg_tcsc *h, const CallPlan &p, const tsg_tcsc::JitVariant &jv, cons
 }
 
 int run_dev(tsg_tcsc *h, const void *dX, const float *db, const float *dalpha, void *dY, int64_t ldY, int M,
-            int N, int K, hipStream_t s, bool prelu, int xtype = tsg::kXF32, int ytype = tsg::kYF32)
+            int N, int K, hipStream_t s, bool prelu, int xtype = tsg::kXF32, int ytype = tsg::kYF32,
+            const float *drs = nullptr, const float *dcs = nullptr)
 {
     if (!h) return fail(TSG_ERR_ARG, "null handle");
     if (!tsg::xtype_ok(xtype))  // refused before anything is enqueued
@@ -560,7 +562,7 @@ int run_dev(tsg_tcsc *h, const void *dX, const float *db, const float *dalpha, v
     std::lock_guard<std::mutex> lk(h->mu);
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     HIP_TRY(hipStreamIsCapturing(s, &cap));
-    const Call c{dX, xtype, db, dalpha, dY, ytype, ldY, M, s, prelu, cap != hipStreamCaptureStatusNone};
+    const Call c{dX, xtype, db, dalpha, drs, dcs, dY, ytype, ldY, M, s, prelu, cap != hipStreamCaptureStatusNone};
     CallPlan p = tsg::plan_call(h->plan, M);
     if (p.is_ell()) return run_ell(h, p, c);
     if (!p.is_jit()) return run_rx(h, p, c);
@@ -1315,6 +1317,25 @@ extern "C" int tcsc_hip_gemm_prelu_dev_xy(tsg_tcsc *h, const void *dX, int xtype
                                           void *stream)
 {
     return run_dev(h, dX, db, dalpha, dY, ldY, M, N, K, (hipStream_t)stream, true, xtype, ytype);
+}
+
+// The epilogue scales (tsg_scale.h): the _xy calls again with a per-row and a
+// per-column scale between the chain and + b[n] (Call::drs, Call::dcs); with
+// both null they are the _xy calls
+extern "C" int tcsc_hip_gemm_dev_scaled(tsg_tcsc *h, const void *dX, int xtype, const float *drow_scale,
+                                        const float *dcol_scale, const float *db, void *dY, int ytype, int64_t ldY,
+                                        int M, int N, int K, void *stream)
+{
+    return run_dev(h, dX, db, nullptr, dY, ldY, M, N, K, (hipStream_t)stream, false, xtype, ytype, drow_scale,
+                   dcol_scale);
+}
+
+extern "C" int tcsc_hip_gemm_prelu_dev_scaled(tsg_tcsc *h, const void *dX, int xtype, const float *drow_scale,
+                                              const float *dcol_scale, const float *db, const float *dalpha, void *dY,
+                                              int ytype, int64_t ldY, int M, int N, int K, void *stream)
+{
+    return run_dev(h, dX, db, dalpha, dY, ldY, M, N, K, (hipStream_t)stream, true, xtype, ytype, drow_scale,
+                   dcol_scale);
 }
 
 extern "C" int tcsc_hip_info(const tsg_tcsc *h, tsg_info *o)

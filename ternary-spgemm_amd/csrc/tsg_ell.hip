@@ -42,6 +42,7 @@
 #include <type_traits>
 
 #include "tsg_internal.h"
+#include "tsg_scale.h"
 #include "tsg_xtype.h"
 #include "tsg_ytype.h"
 
@@ -238,10 +239,15 @@ __device__ __forceinline__ void ell_stage(float *xs, const T *__restrict__ X, in
 
 }  // namespace
 
-template <typename T, int LG, int RPL, int WPG, int LA, bool PRELU>
-__global__ __launch_bounds__(WPG * 64) void tsg_tcsc_ell_kernel(
+// The walk's body: tsg_tcsc_ell_kernel (SCALED = false: rs and cs are null and
+// nothing of them is compiled in) and tsg_tcsc_ell_scaled_kernel (a call with
+// an epilogue scale, tsg_scale.h) -- two kernels, so that the unscaled one is
+// the code, and has the registers, it had before the scales.
+template <typename T, int LG, int RPL, int WPG, int LA, bool PRELU, bool SCALED>
+__device__ __forceinline__ void ell_kernel_body(
     const T *__restrict__ X, const uint4 *__restrict__ ent, const uint2 *__restrict__ tab,
-    const float *__restrict__ b, const float *__restrict__ alpha, float *__restrict__ Y, int64_t ldY, int ytype, int M,
+    const float *__restrict__ b, const float *__restrict__ alpha, const float *__restrict__ rs,
+    const float *__restrict__ cs, float *__restrict__ Y, int64_t ldY, int ytype, int M,
     int N, int K, int C, int nch, int steps, int nsg, int xb, int zr)
 {
     constexpr int MT = LG * RPL;                     // M rows of the tile
@@ -303,6 +309,24 @@ __global__ __launch_bounds__(WPG * 64) void tsg_tcsc_ell_kernel(
     if (slice >= nslices || n >= N) return;
     const float bn = b[n];
     const float an = PRELU ? alpha[n] : 0.0f;
+    if constexpr (SCALED) {
+        // the column scale next to bn, the row scale per r: ((chain * rs[m]) *
+        // cs[n]) + b[n], three roundings (tsg_scale.h)
+        const bool has_rs = rs != nullptr, has_cs = cs != nullptr;
+        const float cn = has_cs ? cs[n] : 0.0f;
+#pragma unroll
+        for (int r = 0; r < RPL; r++) {
+            const int m = m0 + g * RPL + r;
+            if (m >= M) break;
+            float v = scale_bias(y[r], has_rs, has_rs ? rs[m] : 0.0f, has_cs, cn, bn);
+            if (PRELU) v = (v > 0) ? v : an * v;     // comp_prelu.h:57-67
+            if (ytype != kYF32)
+                ystore1(Y, ytype, (size_t)m * (size_t)ldY + n, v);
+            else
+                Y[(size_t)m * (size_t)ldY + n] = v;
+        }
+        return;
+    }
 #pragma unroll
     for (int r = 0; r < RPL; r++) {
         const int m = m0 + g * RPL + r;
@@ -314,6 +338,28 @@ __global__ __launch_bounds__(WPG * 64) void tsg_tcsc_ell_kernel(
         else
             Y[(size_t)m * (size_t)ldY + n] = v;
     }
+}
+
+template <typename T, int LG, int RPL, int WPG, int LA, bool PRELU>
+__global__ __launch_bounds__(WPG * 64) void tsg_tcsc_ell_kernel(
+    const T *__restrict__ X, const uint4 *__restrict__ ent, const uint2 *__restrict__ tab,
+    const float *__restrict__ b, const float *__restrict__ alpha, float *__restrict__ Y, int64_t ldY, int ytype, int M,
+    int N, int K, int C, int nch, int steps, int nsg, int xb, int zr)
+{
+    ell_kernel_body<T, LG, RPL, WPG, LA, PRELU, false>(X, ent, tab, b, alpha, nullptr, nullptr, Y, ldY, ytype, M, N, K, C,
+                                                       nch, steps, nsg, xb, zr);
+}
+
+// ... and with an epilogue scale (launch_ell_la picks it when the call passes one)
+template <typename T, int LG, int RPL, int WPG, int LA, bool PRELU>
+__global__ __launch_bounds__(WPG * 64) void tsg_tcsc_ell_scaled_kernel(
+    const T *__restrict__ X, const uint4 *__restrict__ ent, const uint2 *__restrict__ tab,
+    const float *__restrict__ b, const float *__restrict__ alpha, const float *__restrict__ rs,
+    const float *__restrict__ cs, float *__restrict__ Y, int64_t ldY, int ytype, int M,
+    int N, int K, int C, int nch, int steps, int nsg, int xb, int zr)
+{
+    ell_kernel_body<T, LG, RPL, WPG, LA, PRELU, true>(X, ent, tab, b, alpha, rs, cs, Y, ldY, ytype, M, N, K, C, nch,
+                                                      steps, nsg, xb, zr);
 }
 
 
@@ -358,7 +404,8 @@ struct PcShape {
 template <typename T, int MT, int E, bool PRELU>
 __global__ __launch_bounds__(64 * (MT + E / 8)) void tsg_tcsc_ell_pc_kernel(
     const T *__restrict__ X, const uint4 *__restrict__ ent, const uint2 *__restrict__ tab,
-    const float *__restrict__ b, const float *__restrict__ alpha, float *__restrict__ Y, int64_t ldY, int ytype, int M,
+    const float *__restrict__ b, const float *__restrict__ alpha, const float *__restrict__ rs,
+    const float *__restrict__ cs, float *__restrict__ Y, int64_t ldY, int ytype, int M,
     int N, int K, int C, int nsg)
 {
     using S = PcShape<MT, E>;
@@ -438,6 +485,16 @@ __global__ __launch_bounds__(64 * (MT + E / 8)) void tsg_tcsc_ell_pc_kernel(
             lds_barrier();
         }
         if (n >= N || m0 + r >= M) return;
+        if (ytype & kYScaled) {  // a scaled call (uniform: the launcher's flag; tsg_scale.h)
+            const int yt = ytype & ~kYScaled;
+            float v = scale_bias(y, rs != nullptr, rs ? rs[m0 + r] : 0.0f, cs != nullptr, cs ? cs[n] : 0.0f, b[n]);
+            if (PRELU) v = (v > 0) ? v : alpha[n] * v;   // comp_prelu.h:57-67
+            if (yt != kYF32)
+                ystore1(Y, yt, (size_t)(m0 + r) * (size_t)ldY + n, v);
+            else
+                Y[(size_t)(m0 + r) * (size_t)ldY + n] = v;
+            return;
+        }
         float v = y + b[n];                          // comp.h:63
         if (PRELU) v = (v > 0) ? v : alpha[n] * v;   // comp_prelu.h:57-67
         if (ytype != kYF32)  // a 16-bit Y (uniform): rounded once, one 2-byte store (tsg_ytype.h)
@@ -539,7 +596,7 @@ __global__ __launch_bounds__(64 * (MT + E / 8)) void tsg_tcsc_ell_pc_kernel(
 namespace {
 
 template <typename T, int LG, int RPL, int WPG, int LA>
-int launch_ell_la(const T *X, const uint4 *ent, const uint2 *tab, const float *b, const float *alpha, float *Y,
+int launch_ell_la(const T *X, const uint4 *ent, const uint2 *tab, const float *b, const float *alpha, const float *rs, const float *cs, float *Y,
                   int64_t ldY, int ytype, int M, int N, int K, int C, int nch, int xb, int zr, int prelu, hipStream_t s)
 {
     constexpr int MT = LG * RPL, CPW = 64 / LG;
@@ -548,7 +605,14 @@ int launch_ell_la(const T *X, const uint4 *ent, const uint2 *tab, const float *b
     const int steps = nch == 1 ? 1 : 2 * nch;
     const size_t lds = ell_lds_floats(C, MT, xb, zr) * sizeof(float);
     const dim3 grid((unsigned)(nsg * mtiles)), block(WPG * 64);
-    if (prelu)
+    if (rs || cs) {  // a scaled call: the kernel with the scaled epilogue
+        if (prelu)
+            hipLaunchKernelGGL((tsg_tcsc_ell_scaled_kernel<T, LG, RPL, WPG, LA, true>), grid, block, lds, s, X, ent, tab,
+                               b, alpha, rs, cs, Y, ldY, ytype, M, N, K, C, nch, steps, nsg, xb, zr);
+        else
+            hipLaunchKernelGGL((tsg_tcsc_ell_scaled_kernel<T, LG, RPL, WPG, LA, false>), grid, block, lds, s, X, ent, tab,
+                               b, alpha, rs, cs, Y, ldY, ytype, M, N, K, C, nch, steps, nsg, xb, zr);
+    } else if (prelu)
         hipLaunchKernelGGL((tsg_tcsc_ell_kernel<T, LG, RPL, WPG, LA, true>), grid, block, lds, s, X, ent, tab, b, alpha,
                            Y, ldY, ytype, M, N, K, C, nch, steps, nsg, xb, zr);
     else
@@ -569,12 +633,12 @@ int pick_la()
 }
 
 template <typename T, int LG, int RPL, int WPG>
-int launch_ell_t(const T *X, const uint4 *ent, const uint2 *tab, const float *b, const float *alpha, float *Y,
+int launch_ell_t(const T *X, const uint4 *ent, const uint2 *tab, const float *b, const float *alpha, const float *rs, const float *cs, float *Y,
                  int64_t ldY, int ytype, int M, int N, int K, int C, int nch, int xb, int zr, int prelu, hipStream_t s)
 {
     if (pick_la() == 2)
-        return launch_ell_la<T, LG, RPL, WPG, 2>(X, ent, tab, b, alpha, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
-    return launch_ell_la<T, LG, RPL, WPG, 1>(X, ent, tab, b, alpha, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
+        return launch_ell_la<T, LG, RPL, WPG, 2>(X, ent, tab, b, alpha, rs, cs, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
+    return launch_ell_la<T, LG, RPL, WPG, 1>(X, ent, tab, b, alpha, rs, cs, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
 }
 
 }  // namespace
@@ -595,7 +659,7 @@ namespace {
 constexpr int64_t kEllWideWgs = 224;  // 7/8 of the CUs
 
 template <typename T, int LG, int RPL>
-int launch_lg(const T *X, const uint4 *e, const uint2 *t, const float *b, const float *alpha, float *Y,
+int launch_lg(const T *X, const uint4 *e, const uint2 *t, const float *b, const float *alpha, const float *rs, const float *cs, float *Y,
               int64_t ldY, int ytype, int M, int N, int K, int C, int nch, int xb, int zr, int prelu, hipStream_t s)
 {
     constexpr int MT = LG * RPL, CPW = 64 / LG;
@@ -605,11 +669,11 @@ int launch_lg(const T *X, const uint4 *e, const uint2 *t, const float *b, const 
         const char *v = knob_value("TSG_ELL_WPG");
         return v ? atoi(v) : 0;
     }();
-    if (env_wpg == 4) return launch_ell_t<T, LG, RPL, 4>(X, e, t, b, alpha, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
+    if (env_wpg == 4) return launch_ell_t<T, LG, RPL, 4>(X, e, t, b, alpha, rs, cs, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
     if constexpr (RPL <= 2) {
-        if (env_wpg == 8) return launch_ell_t<T, LG, RPL, 8>(X, e, t, b, alpha, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
+        if (env_wpg == 8) return launch_ell_t<T, LG, RPL, 8>(X, e, t, b, alpha, rs, cs, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
         if (env_wpg == 16)
-            return launch_ell_t<T, LG, RPL, 16>(X, e, t, b, alpha, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
+            return launch_ell_t<T, LG, RPL, 16>(X, e, t, b, alpha, rs, cs, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
     }
     if constexpr (RPL <= 2) {
         auto one_round = [&](int64_t wpg) {  // >= 7/8 of the CUs busy, no second round
@@ -617,14 +681,14 @@ int launch_lg(const T *X, const uint4 *e, const uint2 *t, const float *b, const 
             return wgs >= kEllWideWgs && wgs <= 256 * per_cu;
         };
         if (one_round(16))
-            return launch_ell_t<T, LG, RPL, 16>(X, e, t, b, alpha, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
-        if (one_round(8)) return launch_ell_t<T, LG, RPL, 8>(X, e, t, b, alpha, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
+            return launch_ell_t<T, LG, RPL, 16>(X, e, t, b, alpha, rs, cs, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
+        if (one_round(8)) return launch_ell_t<T, LG, RPL, 8>(X, e, t, b, alpha, rs, cs, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
         if (waves > 256 * per_cu * 8)
-            return launch_ell_t<T, LG, RPL, 16>(X, e, t, b, alpha, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
+            return launch_ell_t<T, LG, RPL, 16>(X, e, t, b, alpha, rs, cs, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
         if (waves > 256 * per_cu * 4)
-            return launch_ell_t<T, LG, RPL, 8>(X, e, t, b, alpha, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
+            return launch_ell_t<T, LG, RPL, 8>(X, e, t, b, alpha, rs, cs, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
     }
-    return launch_ell_t<T, LG, RPL, 4>(X, e, t, b, alpha, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
+    return launch_ell_t<T, LG, RPL, 4>(X, e, t, b, alpha, rs, cs, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
 }
 
 // lanes per column of an M tile: the default, or TSG_ELL_LG (diagnostic sweeps)
@@ -644,7 +708,7 @@ constexpr size_t pc_lds(int C)
 }
 
 template <typename T, int MT, int E>
-int launch_pc_t(const T *X, const uint4 *ent, const uint2 *tab, const float *b, const float *alpha, float *Y,
+int launch_pc_t(const T *X, const uint4 *ent, const uint2 *tab, const float *b, const float *alpha, const float *rs, const float *cs, float *Y,
                 int64_t ldY, int ytype, int M, int N, int K, int C, int prelu, hipStream_t s)
 {
     using S = PcShape<MT, E>;
@@ -653,10 +717,10 @@ int launch_pc_t(const T *X, const uint4 *ent, const uint2 *tab, const float *b, 
     const size_t lds = pc_lds<MT, E>(C);
     const dim3 grid((unsigned)(nsg * mtiles)), block(S::NT);
     if (prelu)
-        hipLaunchKernelGGL((tsg_tcsc_ell_pc_kernel<T, MT, E, true>), grid, block, lds, s, X, ent, tab, b, alpha, Y, ldY, ytype, M,
+        hipLaunchKernelGGL((tsg_tcsc_ell_pc_kernel<T, MT, E, true>), grid, block, lds, s, X, ent, tab, b, alpha, rs, cs, Y, ldY, ytype, M,
                            N, K, C, nsg);
     else
-        hipLaunchKernelGGL((tsg_tcsc_ell_pc_kernel<T, MT, E, false>), grid, block, lds, s, X, ent, tab, b, alpha, Y, ldY, ytype,
+        hipLaunchKernelGGL((tsg_tcsc_ell_pc_kernel<T, MT, E, false>), grid, block, lds, s, X, ent, tab, b, alpha, rs, cs, Y, ldY, ytype,
                            M, N, K, C, nsg);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
@@ -700,10 +764,11 @@ size_t ell_pc_lds_bytes(int variant, int C)
 }
 
 int launch_tcsc_ell_pc(int variant, const void *X, int xtype, const uint32_t *ent, const uint32_t *tab, const float *b,
-                       const float *alpha, void *Yv, int ytype, int64_t ldY, int M, int N, int K, int C, int nch,
+                       const float *alpha, const float *rs, const float *cs, void *Yv, int ytype, int64_t ldY, int M, int N, int K, int C, int nch,
                        int prelu, void *stream)
 {
     float *Y = static_cast<float *>(Yv);  // elements of ytype; the kernels' epilogue casts (tsg_ytype.h)
+    if (rs || cs) ytype |= kYScaled;      // the kernel's one test for a scaled call (tsg_internal.h)
     // one stream per column, X chunk + ring within a workgroup's LDS
     if (nch != 1 || ell_pc_lds_bytes(variant, C) == 0 || ell_pc_lds_bytes(variant, C) > kLdsBytes) return -2;
     hipStream_t s = (hipStream_t)stream;
@@ -713,9 +778,9 @@ int launch_tcsc_ell_pc(int variant, const void *X, int xtype, const uint32_t *en
     return with_xtype(X, xtype, [&](auto *x) {
         using T = std::remove_cv_t<std::remove_pointer_t<decltype(x)>>;
         switch (phase) {
-        case 16: return launch_pc_t<T, 1, 16>(x, e, t, b, alpha, Y, ldY, ytype, M, N, K, C, prelu, s);
-        case 64: return launch_pc_t<T, 1, 64>(x, e, t, b, alpha, Y, ldY, ytype, M, N, K, C, prelu, s);
-        default: return launch_pc_t<T, 1, 32>(x, e, t, b, alpha, Y, ldY, ytype, M, N, K, C, prelu, s);  // 1 consumer, 4 producers
+        case 16: return launch_pc_t<T, 1, 16>(x, e, t, b, alpha, rs, cs, Y, ldY, ytype, M, N, K, C, prelu, s);
+        case 64: return launch_pc_t<T, 1, 64>(x, e, t, b, alpha, rs, cs, Y, ldY, ytype, M, N, K, C, prelu, s);
+        default: return launch_pc_t<T, 1, 32>(x, e, t, b, alpha, rs, cs, Y, ldY, ytype, M, N, K, C, prelu, s);  // 1 consumer, 4 producers
         }
     });
 }
@@ -723,14 +788,14 @@ int launch_tcsc_ell_pc(int variant, const void *X, int xtype, const uint32_t *en
 namespace {
 
 template <typename T>
-int launch_ell_variant(int variant, const T *X, const uint4 *e, const uint2 *t, const float *b, const float *alpha,
+int launch_ell_variant(int variant, const T *X, const uint4 *e, const uint2 *t, const float *b, const float *alpha, const float *rs, const float *cs,
                        float *Y, int64_t ldY, int ytype, int M, int N, int K, int C, int nch, int xb, int zr, int prelu,
                        hipStream_t s)
 {
 #define TSG_ELL_LG(lg, rpl) \
-    case lg: return launch_lg<T, lg, rpl>(X, e, t, b, alpha, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s)
+    case lg: return launch_lg<T, lg, rpl>(X, e, t, b, alpha, rs, cs, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s)
     switch (variant) {
-    case 0: return launch_ell_t<T, 1, 1, 1>(X, e, t, b, alpha, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);  // MT = 1
+    case 0: return launch_ell_t<T, 1, 1, 1>(X, e, t, b, alpha, rs, cs, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);  // MT = 1
     case 1:                                                                                   // MT = 4
         switch (pick_lg(4)) {
             TSG_ELL_LG(4, 1);
@@ -763,7 +828,7 @@ int launch_ell_variant(int variant, const T *X, const uint4 *e, const uint2 *t, 
 }  // namespace
 
 int launch_tcsc_ell(int variant, const void *X, int xtype, const uint32_t *ent, const uint32_t *tab, const float *b,
-                    const float *alpha, void *Yv, int ytype, int64_t ldY, int M, int N, int K, int C, int nch, int xb,
+                    const float *alpha, const float *rs, const float *cs, void *Yv, int ytype, int64_t ldY, int M, int N, int K, int C, int nch, int xb,
                     int zr, int prelu, void *stream)
 {
     float *Y = static_cast<float *>(Yv);  // elements of ytype; the kernels' epilogue casts (tsg_ytype.h)
@@ -774,7 +839,7 @@ int launch_tcsc_ell(int variant, const void *X, int xtype, const uint32_t *ent, 
     const uint4 *e = reinterpret_cast<const uint4 *>(ent);
     const uint2 *t = reinterpret_cast<const uint2 *>(tab);
     return with_xtype(X, xtype, [&](auto *x) {
-        return launch_ell_variant(variant, x, e, t, b, alpha, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
+        return launch_ell_variant(variant, x, e, t, b, alpha, rs, cs, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
     });
 }
 

@@ -29,6 +29,13 @@ inline bool x_quad_aligned(const void *X, int xtype) { return ((uintptr_t)X & (4
 // (tsg_ytype.h).  ldY counts elements of this type; the planner, the work
 // buffer and the staging passes do not look at it.
 enum YType { kYF32 = 0, kYF16 = 1, kYBF16 = 2 };
+// Flag the launchers of the image dispatchers and of the producer/consumer
+// walk set in the kernel's ytype argument when the call passes an epilogue
+// scale (tsg_scale.h): the test for a scaled call reads a register the
+// epilogue holds anyway, and the dispatchers' fp32 path stays behind the one
+// test `ytype != kYF32`.  (The ELL walk has a kernel of its own for scaled
+// calls, tsg_tcsc_ell_scaled_kernel; rx tests the two pointers.)
+constexpr int kYScaled = 0x100;
 inline bool ytype_ok(int ytype) { return ytype >= kYF32 && ytype <= kYBF16; }
 inline size_t ytype_size(int ytype) { return ytype == kYF32 ? 4 : 2; }
 
@@ -242,11 +249,13 @@ struct JitModule {
 // xrow > 0: the 64-row image stages straight from X (xrow floats per row);
 // lastadj: bytes the row layout's last chunk starts below its slot (direct X);
 // xtouch: the per-group code touches (v[lane128 + 1]) spread over the lines;
-// tnear: the code touches' window starts at the step's own position
+// tnear: the code touches' window starts at the step's own position;
+// rs, cs: the epilogue scales of the _scaled calls (float[M], float[N]; either
+// may be null: tsg_scale.h), taken by every kernel below that stores Y
 int launch_tcsc_jit(const JitModule &jm, const float *XT, int Mp, const uint32_t *wcode,
-                    const float *b, const float *alpha, void *Y, int ytype, int64_t ldY, int M, int N, int Npad,
-                    int nch, int prelu, uint32_t *status, int tile_cols, int waves, int gn, int gm, int tmask,
-                    void *stream, int tile_m = kJitTileM, int xrow = 0, int lastadj = 0, int xtouch = 0,
+                    const float *b, const float *alpha, const float *rs, const float *cs, void *Y, int ytype,
+                    int64_t ldY, int M, int N, int Npad, int nch, int prelu, uint32_t *status, int tile_cols,
+                    int waves, int gn, int gm, int tmask, void *stream, int tile_m = kJitTileM, int xrow = 0, int lastadj = 0, int xtouch = 0,
                     int tnear = 0);
 int launch_jit_probe(const JitModule &jm, uint32_t *status, void *stream);
 
@@ -292,7 +301,7 @@ constexpr int kEllSchedZeroRows = 8;
 void build_ell_image(const int32_t *csp, const int32_t *csn, const int32_t *rip, const int32_t *rin, int K, int N,
                      int Cmax, int MT, EllImage &img, int copies = 1, bool sched = false);
 int launch_tcsc_ell(int variant, const void *X, int xtype, const uint32_t *ent, const uint32_t *tab, const float *b,
-                    const float *alpha, void *Y, int ytype, int64_t ldY, int M, int N, int K, int C, int nch, int xb,
+                    const float *alpha, const float *rs, const float *cs, void *Y, int ytype, int64_t ldY, int M, int N, int K, int C, int nch, int xb,
                     int zr, int prelu, void *stream);
 // the producer/consumer walk (tsg_tcsc_ell_pc_kernel) of variant 0 (M = 1) when
 // K fits one chunk and the chunk plus its LDS ring fit kLdsBytes
@@ -300,7 +309,7 @@ int launch_tcsc_ell(int variant, const void *X, int xtype, const uint32_t *ent, 
 constexpr size_t kLdsBytes = 160 * 1024;
 size_t ell_pc_lds_bytes(int variant, int C);
 int launch_tcsc_ell_pc(int variant, const void *X, int xtype, const uint32_t *ent, const uint32_t *tab, const float *b,
-                       const float *alpha, void *Y, int ytype, int64_t ldY, int M, int N, int K, int C, int nch,
+                       const float *alpha, const float *rs, const float *cs, void *Y, int ytype, int64_t ldY, int M, int N, int K, int C, int nch,
                        int prelu, void *stream);
 
 // Environment knobs (csrc/tsg_knobs.cpp): A/B studies and tests, none of
@@ -336,7 +345,7 @@ int launch_transpose_pairs(const void *X, int xtype, float *XP, int M, int K, in
 int launch_transpose_quads(const void *X, int xtype, float *XQ, int M, int K, int Mp, int Kp, int piece_rows,
                            void *stream, int chunk = kJit64Chunk);
 int launch_tcsc_rx(const float *XT, int Mp, const uint32_t *wstart, const uint32_t *ent,
-                   const float *b, const float *alpha, void *Y, int ytype, int64_t ldY, int M, int N, int Npad,
-                   int nch, int prelu, void *stream);
+                   const float *b, const float *alpha, const float *rs, const float *cs, void *Y, int ytype,
+                   int64_t ldY, int M, int N, int Npad, int nch, int prelu, void *stream);
 
 }  // namespace tsg

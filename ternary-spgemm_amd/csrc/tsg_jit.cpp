@@ -934,6 +934,8 @@ namespace {
 constexpr const char *kJitArgsMarker = "tsg_jit_args_ldy";
 // ... and of one whose list goes on with ytype after ldY
 constexpr const char *kJitYtypeMarker = "tsg_jit_args_ytype";
+// ... and with the two epilogue scales rs, cs after ytype
+constexpr const char *kJitScaleMarker = "tsg_jit_args_scale";
 
 // The dispatcher of a stream width: tsg_jit.co (kJitNW columns per wave) or
 // tsg_jit_w<nw>.co (same kernel built with TSG_JIT_NW=nw, Makefile); 4-wave
@@ -1081,6 +1083,13 @@ std::string JitModule::load(const std::vector<uint32_t> &code, int nw, int waves
         return std::string("jit template ") + template_name(nw, waves, r64, half, pair) +
                " predates the dispatcher's ytype argument (no " + kJitYtypeMarker + "); rebuild it";
     }
+    // and for the two scale pointers after ytype
+    if (hipModuleGetFunction(&mark, m, kJitScaleMarker) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipModuleUnload(m);
+        return std::string("jit template ") + template_name(nw, waves, r64, half, pair) +
+               " predates the dispatcher's scale arguments (no " + kJitScaleMarker + "); rebuild it";
+    }
     module = m;
     function = fn;
     probe = pf;
@@ -1104,15 +1113,16 @@ int launch_jit_probe(const JitModule &jm, uint32_t *status, void *stream)
 }
 
 int launch_tcsc_jit(const JitModule &jm, const float *XT, int Mp, const uint32_t *wcode, const float *b,
-                    const float *alpha, void *Y, int ytype, int64_t ldY, int M, int N, int Npad, int nch, int prelu,
-                    uint32_t *status, int tile_cols, int waves, int gn, int gm, int tmask, void *stream,
-                    int tile_m, int xrow, int lastadj, int xtouch, int tnear)
+                    const float *alpha, const float *rs, const float *cs, void *Y, int ytype, int64_t ldY, int M,
+                    int N, int Npad, int nch, int prelu, uint32_t *status, int tile_cols, int waves, int gn, int gm,
+                    int tmask, void *stream, int tile_m, int xrow, int lastadj, int xtouch, int tnear)
 {
     int mtiles = Mp / tile_m, ntiles = Npad / tile_cols;
+    if (rs || cs) ytype |= kYScaled;  // the dispatcher's one test ahead of its fp32 path (tsg_jit_kernel.hip)
     void *params[] = {(void *)&XT, (void *)&Mp, (void *)&wcode, (void *)&b, (void *)&alpha, (void *)&Y,
                       (void *)&M, (void *)&N, (void *)&nch, (void *)&mtiles, (void *)&ntiles, (void *)&prelu,
                       (void *)&status, (void *)&gn, (void *)&gm, (void *)&tmask, (void *)&xrow, (void *)&lastadj,
-                      (void *)&xtouch, (void *)&tnear, (void *)&ldY, (void *)&ytype};
+                      (void *)&xtouch, (void *)&tnear, (void *)&ldY, (void *)&ytype, (void *)&rs, (void *)&cs};
     hipError_t e = hipModuleLaunchKernel((hipFunction_t)jm.function, (unsigned)(mtiles * ntiles), 1, 1,
                                          (unsigned)waves * 64u, 1, 1, 0, (hipStream_t)stream, params, nullptr);
     return e == hipSuccess ? 0 : -1;

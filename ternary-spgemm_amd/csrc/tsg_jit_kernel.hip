@@ -46,6 +46,7 @@
 #include <cstdint>
 
 #include "tsg_jit_map.h"
+#include "tsg_scale.h"
 #include "tsg_ytype.h"
 
 namespace {
@@ -177,13 +178,17 @@ extern "C" __global__ __launch_bounds__(64) void tsg_jit_probe(uint32_t *__restr
 extern "C" __global__ __launch_bounds__(64) void tsg_jit_args_ldy() {}
 // The same for the argument after it, ytype (looked up after the first)
 extern "C" __global__ __launch_bounds__(64) void tsg_jit_args_ytype() {}
+// ... and for the two after that, the epilogue scales rs and cs, with the
+// kYScaled flag in ytype when one of them is passed (looked up last)
+extern "C" __global__ __launch_bounds__(64) void tsg_jit_args_scale() {}
 
 // (the half ring: two workgroups per CU, so at most 256 VGPRs -- two waves per SIMD)
 extern "C" __global__ __launch_bounds__(kJThreads, kJHalf ? 2 : 1) void TSG_JIT_KERNEL_NAME(
     const float *__restrict__ XT, int Mp, const uint32_t *__restrict__ wcode,
     const float *__restrict__ b, const float *__restrict__ alpha, float *__restrict__ Y, int M, int N,
     int nch, int mtiles, int ntiles, int prelu, uint32_t *__restrict__ status, int gn, int gm,
-    int tmask, int xrow, int lastadj, int xtouch, int tnear, int64_t ldY, int ytype)
+    int tmask, int xrow, int lastadj, int xtouch, int tnear, int64_t ldY, int ytype,
+    const float *__restrict__ rs, const float *__restrict__ cs)
 {
     __shared__ __attribute__((aligned(16))) char lds[kJRing * kJBufBytes];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -394,6 +399,35 @@ extern "C" __global__ __launch_bounds__(kJThreads, kJHalf ? 2 : 1) void TSG_JIT_
     if (ncol0 >= N) return;
     if (kJPair && (lane >> 5) != rhalf) return;  // the pair's other wave holds these rows
     if (__builtin_expect(ytype != tsg::kYF32, 0)) {  // (out of line: the fp32 path keeps its layout)
+        if (ytype & tsg::kYScaled) {
+            // a scaled call (uniform; tsg_scale.h): ((chain * rs[m]) * cs[n]) +
+            // b[n], three roundings, then the PReLU and the store of any Y type
+            // (the flag's other bits).  The host sets the flag in ytype when it
+            // passes a scale, so that the test that guards the fp32 path is the
+            // one it was: testing the two pointers there as well costs that
+            // path, on the width-128 dispatcher, 25 VGPR spills to scratch.
+            // The row scale is the lane's own load, one per row; the column
+            // scale is a uniform load next to b[n].
+            const int yt = ytype & ~tsg::kYScaled;
+#pragma unroll
+            for (int r = 0; r < kJRowsPerLane; r++) {
+                const int m = m0 + kJRowsPerLane * lane + r;
+                if (m >= M) continue;
+                // this branch's own copies, fenced like the 16-bit ones below
+                int nc0 = ncol0;
+                const float *bs = b, *alphas = alpha, *rss = rs, *css = cs;
+                asm volatile("" : "+s"(nc0), "+s"(bs), "+s"(alphas), "+s"(rss), "+s"(css));
+                const bool has_rs = rss != nullptr, has_cs = css != nullptr;
+                const float rm = has_rs ? rss[m] : 0.0f;
+                tsg::ystore_seg_any<kJNW>(Y, yt, (size_t)m * (size_t)ldY + nc0, N - nc0, [&](int c) {
+                    const int n = nc0 + c < N ? nc0 + c : N - 1;
+                    float y = tsg::scale_bias(acc_of(c, r), has_rs, rm, has_cs, has_cs ? css[n] : 0.0f, bs[n]);
+                    if (prelu) y = (y > 0) ? y : alphas[n] * y;   // comp_prelu.h:57-67
+                    return y;
+                });
+            }
+            return;
+        }
         // a 16-bit Y (uniform): the same fp32 value, rounded once and stored
         // 8 columns at a time (tsg_ytype.h); ldY counts 16-bit elements
 #pragma unroll

@@ -96,4 +96,54 @@ __device__ __forceinline__ void ystore_seg(void *Y, int ytype, size_t first, int
     }
 }
 
+// The same for a segment of any Y type, fp32 included (the scaled epilogues,
+// tsg_scale.h: one out-of-line copy of the epilogue serves all three types).
+// fp32: a full segment whose first element is 16-byte aligned goes out as
+// float4 stores, anything else as 4-byte stores of the valid elements -- the
+// rule of the kernels' own fp32 stores.  Again val(c) is held once per column
+// and the (uniform) type is looked at per group of 8.
+template <int NW, typename F>
+__device__ __forceinline__ void ystore_seg_any(void *Y, int ytype, size_t first, int nvalid, F &&val)
+{
+    static_assert(NW % 8 == 0, "groups of 8 elements");
+    const bool f32 = ytype == kYF32, bf16 = ytype == kYBF16;
+    // one pointer for both element sizes (a lane holds nothing per type)
+    char *yrow = static_cast<char *>(Y) + first * (f32 ? 4u : 2u);
+    float *yrow32 = reinterpret_cast<float *>(yrow);
+    uint16_t *yrow16 = reinterpret_cast<uint16_t *>(yrow);
+    const bool vec = nvalid >= NW && (((uintptr_t)yrow & 15) == 0);
+#pragma unroll
+    for (int c = 0; c < NW; c += 8) {
+        float v[8];
+#pragma unroll
+        for (int j = 0; j < 8; j++) v[j] = val(c + j);
+        if (f32) {
+            if (vec) {
+                *reinterpret_cast<float4 *>(yrow32 + c) = make_float4(v[0], v[1], v[2], v[3]);
+                *reinterpret_cast<float4 *>(yrow32 + c + 4) = make_float4(v[4], v[5], v[6], v[7]);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 8; j++)
+                    if (c + j < nvalid) yrow32[c + j] = v[j];
+            }
+            continue;
+        }
+        uint32_t w[4];
+        if (bf16) {
+#pragma unroll
+            for (int j = 0; j < 4; j++) w[j] = ypack2<true>(v[2 * j], v[2 * j + 1]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; j++) w[j] = ypack2<false>(v[2 * j], v[2 * j + 1]);
+        }
+        if (vec) {
+            *reinterpret_cast<uint4 *>(yrow16 + c) = make_uint4(w[0], w[1], w[2], w[3]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 8; j++)
+                if (c + j < nvalid) yrow16[c + j] = (uint16_t)(w[j >> 1] >> (16 * (j & 1)));
+        }
+    }
+}
+
 }  // namespace tsg

@@ -102,28 +102,41 @@ class ShardedTCSC:
         sl = cls.draw(K, N, s, seed, rank, world, mode)
         return cls(sl, K, N, rank, world, device, already_sliced=True)
 
-    def forward(self, X, b_full, Y_local=None):
-        """X [M, K] (cuda, fp32, replicated) -> this rank's Y[:, n0:n1]."""
+    def _col_scale(self, col_scale_full):
+        cs = col_scale_full[self.n0:self.n1]
+        return cs if cs.is_contiguous() else cs.contiguous()
+
+    def forward(self, X, b_full, Y_local=None, row_scale=None, col_scale_full=None):
+        """X [M, K] (cuda, fp32, replicated) -> this rank's Y[:, n0:n1].
+        row_scale ([M], replicated) and col_scale_full ([N], sliced [n0:n1]
+        like b_full) are the epilogue scales of TCSCDevice.gemm_torch_scaled;
+        with both None the call is gemm_torch as ever."""
         b = b_full[self.n0:self.n1]
         if not b.is_contiguous():
             b = b.contiguous()
-        return self.local.gemm_torch(X, b, Y_local)
+        if row_scale is None and col_scale_full is None:
+            return self.local.gemm_torch(X, b, Y_local)
+        return self.local.gemm_torch_scaled(X, b, Y_local, row_scale=row_scale,
+                                            col_scale=None if col_scale_full is None else self._col_scale(col_scale_full))
 
-    def forward_into(self, X, b_full, Y_full):
+    def forward_into(self, X, b_full, Y_full, row_scale=None, col_scale_full=None):
         """X [M, K] -> this rank's block written straight into Y_full[:, n0:n1]
         (Y_full [M, N] row-major on this rank's GPU; the kernel's output row
         stride is N, tcsc_hip_gemm_dev_ld); returns that view.  No scratch
         block, no reorder: shards of one process (a loop over ShardedTCSC
         objects on one GPU) fill one Y_full.  The multi-rank gather still goes
         through forward + GatherPipeline (all_gather_into_tensor needs a
-        contiguous input)."""
+        contiguous input).  row_scale and col_scale_full as in forward."""
         if Y_full.dim() != 2 or tuple(Y_full.shape) != (X.shape[0], self.N) or not Y_full.is_contiguous():
             raise T.TSGError(1, "forward_into", f"Y_full must be a row-major [{X.shape[0]}, {self.N}] tensor, got "
                                                 f"{list(Y_full.shape)} with strides {Y_full.stride()}")
         b = b_full[self.n0:self.n1]
         if not b.is_contiguous():
             b = b.contiguous()
-        return self.local.gemm_torch_into(X, b, Y_full[:, self.n0:self.n1])
+        if row_scale is None and col_scale_full is None:
+            return self.local.gemm_torch_into(X, b, Y_full[:, self.n0:self.n1])
+        return self.local.gemm_torch_scaled(X, b, Y_full[:, self.n0:self.n1], row_scale=row_scale,
+                                            col_scale=None if col_scale_full is None else self._col_scale(col_scale_full))
 
 
 def allgather_columns(Y_local, N: int, world: int, group=None):

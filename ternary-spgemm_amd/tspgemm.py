@@ -51,6 +51,7 @@ EXPORTED_SYMBOLS = (
     "tcsc_hip_gemm_dev_ld", "tcsc_hip_gemm_prelu_dev_ld",
     "tcsc_hip_gemm_dev_x", "tcsc_hip_gemm_prelu_dev_x",
     "tcsc_hip_gemm_dev_xy", "tcsc_hip_gemm_prelu_dev_xy",
+    "tcsc_hip_gemm_dev_scaled", "tcsc_hip_gemm_prelu_dev_scaled",
 )
 
 # enum tsg_xtype (include/ternary_spgemm.h): element type of X on the _x calls
@@ -113,6 +114,10 @@ def lib() -> C.CDLL:
     L.tcsc_hip_gemm_dev_xy.argtypes = [H, vp, C.c_int, vp, vp, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, vp]
     L.tcsc_hip_gemm_prelu_dev_xy.argtypes = [H, vp, C.c_int, vp, vp, vp, C.c_int, C.c_int64, C.c_int, C.c_int,
                                              C.c_int, vp]
+    L.tcsc_hip_gemm_dev_scaled.argtypes = [H, vp, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int64, C.c_int, C.c_int,
+                                           C.c_int, vp]
+    L.tcsc_hip_gemm_prelu_dev_scaled.argtypes = [H, vp, C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_int64, C.c_int,
+                                                 C.c_int, C.c_int, vp]
     L.tcsc_hip_reserve.argtypes = [H, C.c_int]
     L.tcsc_hip_info.argtypes = [H, C.POINTER(tsg_info)]
     L.tcsc_hip_to_dense.argtypes = [H, vp, C.c_int, C.c_int]
@@ -670,7 +675,35 @@ class TCSCDevice:
         the fp32 value rounded once, in the kernel's epilogue.  Returns Y."""
         return self._torch_xy("gemm_torch_xy", X, b, Y, alpha, out_dtype, narrow_y=True)
 
-    def _torch_xy(self, where, X, b, Y, alpha, out_dtype, narrow_y):
+    def gemm_dev_scaled(self, dX: int, xtype: int, db: int, dY: int, ytype: int, M: int, stream: int = 0,
+                        dalpha: Optional[int] = None, ldY: Optional[int] = None,
+                        drow_scale: Optional[int] = None, dcol_scale: Optional[int] = None) -> None:
+        """gemm_dev_xy with the epilogue scales (tcsc_hip_gemm_dev_scaled):
+        Y[m, n] = ((chain * drow_scale[m]) * dcol_scale[n]) + db[n] in fp32, one
+        rounding per operation, then the PReLU and the rounding to ytype.
+        drow_scale is float[M], dcol_scale float[N] (device pointers); None =
+        that multiply is not performed, both None = gemm_dev_xy."""
+        ld = self.N if ldY is None else int(ldY)
+        if dalpha is None:
+            _check(lib().tcsc_hip_gemm_dev_scaled(self._h, dX, int(xtype), drow_scale, dcol_scale, db, dY, int(ytype),
+                                                  ld, M, self.N, self.K, stream or None), "tcsc_hip_gemm_dev_scaled")
+        else:
+            _check(lib().tcsc_hip_gemm_prelu_dev_scaled(self._h, dX, int(xtype), drow_scale, dcol_scale, db, dalpha,
+                                                        dY, int(ytype), ld, M, self.N, self.K, stream or None),
+                   "tcsc_hip_gemm_prelu_dev_scaled")
+
+    def gemm_torch_scaled(self, X, b, Y=None, alpha=None, out_dtype=None, row_scale=None, col_scale=None):
+        """gemm_torch_xy with a per-row and a per-column scale between the chain
+        and + b: row_scale is None or a contiguous float32 [M] tensor on the
+        handle's device (the dequantisation scale of int8 activations),
+        col_scale None or a contiguous float32 [N] tensor (the weight scale).
+        Y[m, n] = ((chain * row_scale[m]) * col_scale[n]) + b[n], each operation
+        rounded to fp32 on its own, then the PReLU and the one rounding to Y's
+        dtype.  With both None it is gemm_torch_xy bit for bit.  Returns Y."""
+        return self._torch_xy("gemm_torch_scaled", X, b, Y, alpha, out_dtype, narrow_y=True, scaled=True,
+                              row_scale=row_scale, col_scale=col_scale)
+
+    def _torch_xy(self, where, X, b, Y, alpha, out_dtype, narrow_y, scaled=False, row_scale=None, col_scale=None):
         import torch
         dev = torch.device("cuda", self.device)
         ytypes = {torch.float32: TSG_Y_F32}
@@ -687,9 +720,12 @@ class TCSCDevice:
             raise TSGError(1, where, f"X must be a contiguous float32, float16, bfloat16 or int8 "
                                               f"{[M, self.K]} tensor on {dev}, got {X.dtype} {list(X.shape)} on "
                                               f"{X.device}{'' if X.is_contiguous() else ' (non-contiguous)'}")
-        for name, t, shape in (("b", b, (self.N,)), ("alpha", alpha, (self.N,))):
+        for name, t, shape in (("b", b, (self.N,)), ("alpha", alpha, (self.N,)), ("row_scale", row_scale, (M,)),
+                               ("col_scale", col_scale, (self.N,))):
             if t is None:
                 continue
+            if name.endswith("_scale") and not isinstance(t, torch.Tensor):
+                raise TSGError(1, where, f"{name} must be a tensor, got {type(t)}")
             if t.dtype != torch.float32 or t.device != dev or not t.is_contiguous() or tuple(t.shape) != shape:
                 raise TSGError(1, where, f"{name} must be a contiguous float32 {list(shape)} tensor on "
                                                   f"{dev}, got {t.dtype} {list(t.shape)} on {t.device}"
@@ -712,7 +748,11 @@ class TCSCDevice:
             raise TSGError(1, where, f"Y's rows overlap: stride(0) = {ldY} < N = {self.N}")
         stream = torch.cuda.current_stream(dev).cuda_stream
         dalpha = None if alpha is None else alpha.data_ptr()
-        if narrow_y:
+        if scaled:
+            self.gemm_dev_scaled(X.data_ptr(), xtypes[X.dtype], b.data_ptr(), Y.data_ptr(), ytypes[Y.dtype], M, stream,
+                                 dalpha, ldY=ldY, drow_scale=None if row_scale is None else row_scale.data_ptr(),
+                                 dcol_scale=None if col_scale is None else col_scale.data_ptr())
+        elif narrow_y:
             self.gemm_dev_xy(X.data_ptr(), xtypes[X.dtype], b.data_ptr(), Y.data_ptr(), ytypes[Y.dtype], M, stream,
                              dalpha, ldY=ldY)
         else:
