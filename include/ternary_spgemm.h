@@ -296,6 +296,58 @@ int tcsc_hip_gemm_prelu_dev_scaled(tsg_tcsc *h, const void *dX, int xtype, const
                                    const float *dcol_scale, const float *db, const float *dalpha, void *dY,
                                    int ytype, int64_t ldY, int M, int N, int K, void *stream);
 
+/* The _scaled calls with the int8 activations and their per-row scale made
+ * inside the call: per-row (per-token) symmetric int8 quantisation of an fp32,
+ * fp16 or bf16 X, fused into the pass that stages X.  With the int8 X and the
+ * row scale of the _scaled calls this is a W1.58A8 linear layer from
+ * activations in their own type, one call, no int8 copy of X in memory.
+ *
+ * Contract.  All arithmetic is fp32 on the widened X (the widening is exact),
+ * one rounding per operation, both divisions IEEE correctly rounded:
+ *
+ *   amax[m] = max_k |x[m, k]|                     (0 for K = 0)
+ *   a       = max(amax[m], 1e-5f)
+ *   inv     = 127.0f / a
+ *   deq[m]  = a / 127.0f
+ *   q[m, k] = min(max(rintf(x[m, k] * inv), -127.0f), 127.0f)   ties to even
+ *   Y       = what tcsc_hip_gemm_[prelu_]dev_scaled stores for the int8 X = q,
+ *             drow_scale = deq and the same dcol_scale, db, dalpha, ytype and
+ *             ldY -- bit for bit.
+ *
+ * xtype is TSG_X_F32, TSG_X_F16 or TSG_X_BF16; TSG_X_I8 is TSG_ERR_ARG with a
+ * message, nothing enqueued (an int8 X has its scale already: _scaled).
+ * drow_scale_out may be NULL; otherwise deq is stored to it, float[M] of device
+ * memory that needs only 4-byte alignment, and only [0, M) is written.
+ * dcol_scale may be NULL: its multiply is then not performed, as on _scaled.
+ * A zero row gives q = 0 and Y[m, n] = db[n] (after the PReLU and the cast).
+ * A row that holds an inf or a NaN: its own Y row and deq[m] are unspecified;
+ * nothing faults, and every other row is bit for bit what it is without it.
+ * (rintf(x * inv) can be -0 where an int8 holds 0; a chain starts at +0 and is
+ * never -0, so both give the same bits.)
+ * How it runs.  A row pass (one wave per row) finds amax and writes inv and
+ * deq to a per-handle scratch; the staging pass of the kernel an M picks then
+ * quantises each value it loads, so the staged copy holds integer-valued fp32
+ * and the kernel runs the chains of an int8 X with the scratch's deq as its
+ * row scale.  Such a call is always staged (never the direct-X path).  A
+ * small-M walk reads X in place: for it the row pass also writes q as int8 to
+ * the scratch and the walk runs on that.  Two launches more than _scaled at
+ * most, no synchronisation.
+ * As on _scaled: ldY, dY's alignment and the written-range guarantee, the
+ * 16-bit neighbour in a shared dword included; stream semantics; isolation
+ * from memory outside the operands and from earlier calls; the kernel and
+ * image an M picks.  The scratch (two floats per row, and M * K bytes for a
+ * walk) is the handle's, grow-only and shared by every stream exactly like the
+ * work buffer: tcsc_hip_reserve(h, max_M) sizes it, and a call that would grow
+ * it during stream capture is TSG_ERR_ARG naming tcsc_hip_reserve.
+ * Out of scope: asymmetric or int4 quantisation, a caller's clip value, the
+ * host-pointer calls, the plugin header.  Extension: no reference counterpart. */
+int tcsc_hip_gemm_dev_actquant(tsg_tcsc *h, const void *dX, int xtype, float *drow_scale_out,
+                               const float *dcol_scale, const float *db, void *dY, int ytype, int64_t ldY,
+                               int M, int N, int K, void *stream);
+int tcsc_hip_gemm_prelu_dev_actquant(tsg_tcsc *h, const void *dX, int xtype, float *drow_scale_out,
+                                     const float *dcol_scale, const float *db, const float *dalpha, void *dY,
+                                     int ytype, int64_t ldY, int M, int N, int K, void *stream);
+
 /* Pre-allocates the per-handle work buffer for row counts up to max_M and, on
  * the weight-compiled kernel, compiles every code image a call with M <= max_M
  * rows runs (and the small-M images), so no later such call allocates or

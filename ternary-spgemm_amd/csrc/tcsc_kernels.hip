@@ -15,6 +15,10 @@
 // the staged copy never see the type.  The vector forms read one quad (four
 // consecutive k of a row) per load: 16 B of fp32, 8 B of a 16-bit type, 4 B of
 // int8; they need X aligned to 4 elements and K % 4 == 0 (x_quad_aligned).
+// Every staging pass is also a template on Q: an actquant call's pass
+// quantises each value it loads, xquant(v, inv[m]) (tsg_actquant.h), with
+// inv[m] from tsg_row_absmax_kernel, the row pass that runs before it; Q =
+// false is the pass as it was.
 // tsg_tcsc_rx_kernel: the register-X walk, the fallback when a W is too large
 //   for one weight-compiled image (> ~300 M nonzeros on one handle) or the
 //   generated image cannot be loaded (tsg_capi.cpp create_impl).
@@ -22,6 +26,7 @@
 
 #include <type_traits>
 
+#include "tsg_actquant.h"
 #include "tsg_internal.h"
 #include "tsg_scale.h"
 #include "tsg_xtype.h"
@@ -30,10 +35,10 @@
 namespace tsg {
 
 // ------------------------------------------------------------------ kernel 1 --
-template <typename T>
+template <typename T, bool Q>
 __global__ __launch_bounds__(256) void tsg_transpose_kernel(const T *__restrict__ X,
                                                             float *__restrict__ XT, int M, int K,
-                                                            int Mp, int Kp)
+                                                            int Mp, int Kp, const float *__restrict__ inv)
 {
     __shared__ float tile[64][65];
     const int k0 = blockIdx.x * 64, m0 = blockIdx.y * 64;
@@ -41,7 +46,9 @@ __global__ __launch_bounds__(256) void tsg_transpose_kernel(const T *__restrict_
 #pragma unroll
     for (int i = 0; i < 16; i++) {
         const int m = m0 + ty + 4 * i, k = k0 + tx;
-        tile[ty + 4 * i][tx] = (m < M && k < K) ? xload1(X + (size_t)m * K + k) : 0.0f;
+        float v = (m < M && k < K) ? xload1(X + (size_t)m * K + k) : 0.0f;
+        if (Q && m < M) v = xquant(v, inv[m]);
+        tile[ty + 4 * i][tx] = v;
     }
     __syncthreads();
 #pragma unroll
@@ -54,10 +61,10 @@ __global__ __launch_bounds__(256) void tsg_transpose_kernel(const T *__restrict_
 // Same transpose with a quad per load and 16-byte stores (K % 4 == 0 and X
 // aligned to 4 elements): each lane loads 4 consecutive k of one m row and stores 4
 // consecutive m of one X^T row -- a quarter of the memory instructions.
-template <typename T>
+template <typename T, bool Q>
 __global__ __launch_bounds__(256) void tsg_transpose4_kernel(const T *__restrict__ X,
                                                              float *__restrict__ XT, int M, int K,
-                                                             int Mp, int Kp)
+                                                             int Mp, int Kp, const float *__restrict__ inv)
 {
     __shared__ float tile[64][65];
     const int k0 = blockIdx.x * 64, m0 = blockIdx.y * 64;
@@ -66,7 +73,10 @@ __global__ __launch_bounds__(256) void tsg_transpose4_kernel(const T *__restrict
     for (int i = 0; i < 4; i++) {
         const int ml = r + 16 * i, m = m0 + ml, k = k0 + c4;
         float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        if (m < M && k < K) v = xload4(X + (size_t)m * K + k);  // K % 4 == 0
+        if (m < M && k < K) {
+            v = xload4(X + (size_t)m * K + k);  // K % 4 == 0
+            if (Q) v = xquant4(v, inv[m]);
+        }
         tile[ml][c4] = v.x;
         tile[ml][c4 + 1] = v.y;
         tile[ml][c4 + 2] = v.z;
@@ -89,10 +99,10 @@ __global__ __launch_bounds__(256) void tsg_transpose4_kernel(const T *__restrict
 // VEC: K % 4 == 0 and X aligned to 4 elements), stores 16 B per lane, consecutive
 // lanes on consecutive mp (coalesced 512-B runs per pair row).  HBM-bound:
 // 8 * M * K bytes.
-template <typename T, bool VEC>
+template <typename T, bool VEC, bool Q>
 __global__ __launch_bounds__(256) void tsg_transpose_pairs_kernel(const T *__restrict__ X,
                                                                   float *__restrict__ XP, int M, int K,
-                                                                  int Mp, int Kp)
+                                                                  int Mp, int Kp, const float *__restrict__ inv)
 {
     __shared__ float tile[64][65];  // [m][k]
     const int k0 = blockIdx.x * 64, m0 = blockIdx.y * 64;
@@ -102,7 +112,10 @@ __global__ __launch_bounds__(256) void tsg_transpose_pairs_kernel(const T *__res
         for (int i = 0; i < 4; i++) {
             const int ml = r + 16 * i, m = m0 + ml, k = k0 + c4;
             float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            if (m < M && k < K) v = xload4(X + (size_t)m * K + k);  // K % 4 == 0
+            if (m < M && k < K) {
+            v = xload4(X + (size_t)m * K + k);  // K % 4 == 0
+            if (Q) v = xquant4(v, inv[m]);
+        }
             tile[ml][c4] = v.x;
             tile[ml][c4 + 1] = v.y;
             tile[ml][c4 + 2] = v.z;
@@ -113,7 +126,9 @@ __global__ __launch_bounds__(256) void tsg_transpose_pairs_kernel(const T *__res
 #pragma unroll
         for (int i = 0; i < 16; i++) {
             const int m = m0 + ty + 4 * i, k = k0 + tx;
-            tile[ty + 4 * i][tx] = (m < M && k < K) ? xload1(X + (size_t)m * K + k) : 0.0f;
+            float v = (m < M && k < K) ? xload1(X + (size_t)m * K + k) : 0.0f;
+            if (Q && m < M) v = xquant(v, inv[m]);
+            tile[ty + 4 * i][tx] = v;
         }
     }
     __syncthreads();
@@ -131,10 +146,10 @@ __global__ __launch_bounds__(256) void tsg_transpose_pairs_kernel(const T *__res
 }
 
 // X [M][K] -> the blocked k-quad layout of the 64-row image (tsg_internal.h),
-// PR rows per piece (16 or 8) and Q = 64 / PR quads: the 1-KiB piece pr = Q qg
+// PR rows per piece (16 or 8) and QP = 64 / PR quads: the 1-KiB piece pr = QP qg
 // + rg of (chunk c, M tile t) at ((c * Mt + t) * U + pr) KiB (U = 48 units per
 // chunk, 24 for the half ring) holds, in 16-B
-// lane slot j, X[64 t + PR rg + j % PR][4 (48 c + Q qg + j / PR) .. +3] -- zero
+// lane slot j, X[64 t + PR rg + j % PR][4 (48 c + QP qg + j / PR) .. +3] -- zero
 // past M or K -- so the kernel's DMA pieces are coalesced 1-KiB reads.  Every
 // slot is 16 contiguous bytes of a row of X, so this is a gather-copy, not a
 // transpose: one wave writes one whole piece (1 KiB, one store per lane) from
@@ -142,13 +157,14 @@ __global__ __launch_bounds__(256) void tsg_transpose_pairs_kernel(const T *__res
 // 128-B line is the next piece's, copied by the neighbouring workgroup); no
 // LDS, no barrier.  A workgroup copies 4 consecutive pieces of one (chunk, M
 // tile).  HBM-bound: 8 * Mp * Kp bytes.
-template <typename T, bool VEC, int PR>
+template <typename T, bool VEC, int PR, bool Q>
 __global__ __launch_bounds__(256) void tsg_transpose_quads_kernel(const T *__restrict__ X,
                                                                   float *__restrict__ XQ, int M, int K,
-                                                                  int Mp, int Kp, int units)
+                                                                  int Mp, int Kp, int units,
+                                                                  const float *__restrict__ inv)
 {
     // units: 1-KiB pieces per (chunk, M tile) -- 48, or 24 for the half ring
-    constexpr int Q = 64 / PR;
+    constexpr int QP = 64 / PR;
     const int Mt = Mp >> 6, nch = Kp / (4 * units), groups = units / 4;
     // workgroup order (M tile * nch + chunk) * 12 + piece group: the workgroups
     // in flight read a few M tiles' rows end to end (long runs of each row), not
@@ -157,9 +173,9 @@ __global__ __launch_bounds__(256) void tsg_transpose_quads_kernel(const T *__res
     const int tc = blk / groups, pr = (blk % groups) * 4 + (threadIdx.x >> 6);
     const int t = tc / nch, c = tc % nch, j = threadIdx.x & 63;
     const int ct = c * Mt + t;
-    const int qg = pr / Q, rg = pr % Q;
+    const int qg = pr / QP, rg = pr % QP;
     const int m = 64 * t + PR * rg + (j % PR);
-    const int k = 4 * (units * c + Q * qg + j / PR);
+    const int k = 4 * (units * c + QP * qg + j / PR);
     float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     if (m < M) {
         const T *row = X + (size_t)m * K;
@@ -171,6 +187,8 @@ __global__ __launch_bounds__(256) void tsg_transpose_quads_kernel(const T *__res
             if (k + 2 < K) v.z = xload1(row + k + 2);
             if (k + 3 < K) v.w = xload1(row + k + 3);
         }
+        // (a slot past K holds +0, and xquant(+0) is +0)
+        if (Q) v = xquant4(v, inv[m]);
     }
     *reinterpret_cast<float4 *>(XQ + ((size_t)ct * units + pr) * 256 + (size_t)j * 4) = v;
 }
@@ -183,10 +201,10 @@ __global__ __launch_bounds__(256) void tsg_transpose_quads_kernel(const T *__res
 // of a row of X, so this is a gather-copy of row runs (no transpose): reads
 // and writes both run along rows.  Four workgroups per (chunk, M tile), 752
 // slots each.  HBM-bound: 2 * 4 * Mp * Kp bytes.
-template <typename T, bool VEC>
+template <typename T, bool VEC, bool Q>
 __global__ __launch_bounds__(256) void tsg_transpose_rows_kernel(const T *__restrict__ X,
                                                                  float *__restrict__ XR, int M, int K, int Mp,
-                                                                 int nch)
+                                                                 int nch, const float *__restrict__ inv)
 {
     constexpr int kQ = 47, kSlots = 64 * kQ, kPer = kSlots / 4;  // 752 slots per workgroup
     const int Mt = Mp >> 6;
@@ -210,8 +228,61 @@ __global__ __launch_bounds__(256) void tsg_transpose_rows_kernel(const T *__rest
                 if (k + 2 < K) v.z = xload1(row + k + 2);
                 if (k + 3 < K) v.w = xload1(row + k + 3);
             }
+            if (Q) v = xquant4(v, inv[m]);
         }
         *reinterpret_cast<float4 *>(dst + (size_t)slot * 4) = v;
+    }
+}
+
+// The row pass of an actquant call (tsg_actquant.h): one wave per row of X,
+// four rows per workgroup.  Each lane keeps fmaxf(fabsf()) of the elements it
+// loads (a quad per load when VEC: K % 4 == 0 and X aligned to 4 elements), an
+// xor butterfly leaves the row's maximum in every lane (max is exact and
+// associative: the reduction's shape does not matter, and a NaN is never the
+// larger operand), and lane 0 stores inv[m], deq[m] and, when given, out[m].
+// Q8: the call runs a small-M walk, which reads X in place -- every lane then
+// reads its elements again (still in cache) and stores q as int8, row-major
+// [M][K], four per store when VEC (q8 is aligned to 4 B and K % 4 == 0); the
+// walk runs on q8 as an int8-X scaled call.  K = 0: no loads, amax = 0.
+template <typename T, bool VEC, bool Q8>
+__global__ __launch_bounds__(256) void tsg_row_absmax_kernel(const T *__restrict__ X, int M, int K,
+                                                             float *__restrict__ inv, float *__restrict__ deq,
+                                                             float *__restrict__ out, int8_t *__restrict__ q8)
+{
+    const int lane = threadIdx.x & 63;
+    const int m = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (m >= M) return;  // (whole waves: no barrier follows)
+    const T *row = X + (size_t)m * K;
+    float amax = 0.0f;
+    if (VEC) {
+        for (int k = 4 * lane; k < K; k += 256) {
+            const float4 v = xload4(row + k);
+            amax = fmaxf(amax, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
+        }
+    } else {
+        for (int k = lane; k < K; k += 64) amax = fmaxf(amax, fabsf(xload1(row + k)));
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) amax = fmaxf(amax, __shfl_xor(amax, d, 64));
+    float iv, dq;
+    actquant_scales(amax, iv, dq);
+    if (lane == 0) {
+        inv[m] = iv;
+        deq[m] = dq;
+        if (out) out[m] = dq;
+    }
+    if (Q8) {
+        int8_t *qrow = q8 + (size_t)m * K;
+        if (VEC) {
+            for (int k = 4 * lane; k < K; k += 256) {
+                const float4 v = xquant4(xload4(row + k), iv);
+                const uint32_t w = ((uint32_t)(int)v.x & 0xffu) | (((uint32_t)(int)v.y & 0xffu) << 8) |
+                                   (((uint32_t)(int)v.z & 0xffu) << 16) | ((uint32_t)(int)v.w << 24);
+                *reinterpret_cast<uint32_t *>(qrow + k) = w;
+            }
+        } else {
+            for (int k = lane; k < K; k += 64) qrow[k] = (int8_t)(int)xquant(xload1(row + k), iv);
+        }
     }
 }
 
@@ -407,22 +478,42 @@ __global__ __launch_bounds__(kRxWaves * 64, 8 / kRxWaves) void tsg_tcsc_rx_kerne
 }
 
 // ---------------------------------------------------------------- launchers --
-int launch_transpose(const void *X, int xtype, float *XT, int M, int K, int Mp, int Kp, void *stream)
+// Calls f(std::bool_constant<Q>) with Q = whether the staging pass quantises
+// (inv given, tsg_actquant.h).  An int8 X is never quantised (the C-ABI
+// refuses it), so that combination is not instantiated.
+template <typename T, typename F>
+int with_quant(const float *inv, F &&f)
+{
+    if constexpr (std::is_same_v<T, xi8>) {
+        return inv ? -1 : f(std::false_type{});
+    } else {
+        return inv ? f(std::true_type{}) : f(std::false_type{});
+    }
+}
+
+int launch_transpose(const void *X, int xtype, float *XT, int M, int K, int Mp, int Kp, void *stream,
+                     const float *inv)
 {
     dim3 grid((unsigned)((Kp + 63) / 64), (unsigned)(Mp / 64));
     const bool vec = K % 4 == 0 && x_quad_aligned(X, xtype);
     return with_xtype(X, xtype, [&](auto *x) {
         using T = std::remove_cv_t<std::remove_pointer_t<decltype(x)>>;
-        if (vec)
-            hipLaunchKernelGGL(tsg_transpose4_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, x, XT, M, K, Mp, Kp);
-        else
-            hipLaunchKernelGGL(tsg_transpose_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, x, XT, M, K, Mp, Kp);
-        return hipGetLastError() == hipSuccess ? 0 : -1;
+        return with_quant<T>(inv, [&](auto q) {
+            constexpr bool Q = decltype(q)::value;
+            if (vec)
+                hipLaunchKernelGGL((tsg_transpose4_kernel<T, Q>), grid, dim3(256), 0, (hipStream_t)stream, x, XT, M, K,
+                                   Mp, Kp, inv);
+            else
+                hipLaunchKernelGGL((tsg_transpose_kernel<T, Q>), grid, dim3(256), 0, (hipStream_t)stream, x, XT, M, K,
+                                   Mp, Kp, inv);
+            return hipGetLastError() == hipSuccess ? 0 : -1;
+        });
     });
 }
 
 
-int launch_transpose_pairs(const void *X, int xtype, float *XP, int M, int K, int Mp, int Kp, void *stream)
+int launch_transpose_pairs(const void *X, int xtype, float *XP, int M, int K, int Mp, int Kp, void *stream,
+                           const float *inv)
 {
     // Mp is a multiple of 128 (the jit M tile) and Kp of 96: the 64 x 64 tiles
     // cover [0, Kp) x [0, Mp) exactly in m and up to 32 pad rows in k
@@ -430,18 +521,21 @@ int launch_transpose_pairs(const void *X, int xtype, float *XP, int M, int K, in
     const bool vec = K % 4 == 0 && x_quad_aligned(X, xtype);
     return with_xtype(X, xtype, [&](auto *x) {
         using T = std::remove_cv_t<std::remove_pointer_t<decltype(x)>>;
-        if (vec)
-            hipLaunchKernelGGL((tsg_transpose_pairs_kernel<T, true>), grid, dim3(256), 0, (hipStream_t)stream, x, XP, M,
-                               K, Mp, Kp);
-        else
-            hipLaunchKernelGGL((tsg_transpose_pairs_kernel<T, false>), grid, dim3(256), 0, (hipStream_t)stream, x, XP,
-                               M, K, Mp, Kp);
-        return hipGetLastError() == hipSuccess ? 0 : -1;
+        return with_quant<T>(inv, [&](auto q) {
+            constexpr bool Q = decltype(q)::value;
+            if (vec)
+                hipLaunchKernelGGL((tsg_transpose_pairs_kernel<T, true, Q>), grid, dim3(256), 0, (hipStream_t)stream, x,
+                                   XP, M, K, Mp, Kp, inv);
+            else
+                hipLaunchKernelGGL((tsg_transpose_pairs_kernel<T, false, Q>), grid, dim3(256), 0, (hipStream_t)stream,
+                                   x, XP, M, K, Mp, Kp, inv);
+            return hipGetLastError() == hipSuccess ? 0 : -1;
+        });
     });
 }
 
 int launch_transpose_quads(const void *X, int xtype, float *XQ, int M, int K, int Mp, int Kp, int piece_rows,
-                           void *stream, int chunk)
+                           void *stream, int chunk, const float *inv)
 {
     hipStream_t s = (hipStream_t)stream;
     const bool vec = K % 4 == 0 && x_quad_aligned(X, xtype);
@@ -452,9 +546,12 @@ int launch_transpose_quads(const void *X, int xtype, float *XQ, int M, int K, in
         if (blocks >= ((int64_t)1 << 31)) return -1;
         return with_xtype(X, xtype, [&](auto *x) {
             using T = std::remove_cv_t<std::remove_pointer_t<decltype(x)>>;
-            if (vec) hipLaunchKernelGGL((tsg_transpose_rows_kernel<T, true>), dim3((unsigned)blocks), dim3(256), 0, s, x, XQ, M, K, Mp, nch);
-            else hipLaunchKernelGGL((tsg_transpose_rows_kernel<T, false>), dim3((unsigned)blocks), dim3(256), 0, s, x, XQ, M, K, Mp, nch);
-            return hipGetLastError() == hipSuccess ? 0 : -1;
+            return with_quant<T>(inv, [&](auto q) {
+                constexpr bool Q = decltype(q)::value;
+                if (vec) hipLaunchKernelGGL((tsg_transpose_rows_kernel<T, true, Q>), dim3((unsigned)blocks), dim3(256), 0, s, x, XQ, M, K, Mp, nch, inv);
+                else hipLaunchKernelGGL((tsg_transpose_rows_kernel<T, false, Q>), dim3((unsigned)blocks), dim3(256), 0, s, x, XQ, M, K, Mp, nch, inv);
+                return hipGetLastError() == hipSuccess ? 0 : -1;
+            });
         });
     }
     // Mp is a multiple of 64 (the 64-row image's M tile) and Kp of 192 (its
@@ -468,14 +565,45 @@ int launch_transpose_quads(const void *X, int xtype, float *XQ, int M, int K, in
     dim3 grid((unsigned)blocks);
     return with_xtype(X, xtype, [&](auto *x) {
         using T = std::remove_cv_t<std::remove_pointer_t<decltype(x)>>;
-        if (piece_rows == 16) {
-            if (vec) hipLaunchKernelGGL((tsg_transpose_quads_kernel<T, true, 16>), grid, dim3(256), 0, s, x, XQ, M, K, Mp, Kp, units);
-            else hipLaunchKernelGGL((tsg_transpose_quads_kernel<T, false, 16>), grid, dim3(256), 0, s, x, XQ, M, K, Mp, Kp, units);
+        return with_quant<T>(inv, [&](auto q) {
+            constexpr bool Q = decltype(q)::value;
+            if (piece_rows == 16) {
+                if (vec) hipLaunchKernelGGL((tsg_transpose_quads_kernel<T, true, 16, Q>), grid, dim3(256), 0, s, x, XQ, M, K, Mp, Kp, units, inv);
+                else hipLaunchKernelGGL((tsg_transpose_quads_kernel<T, false, 16, Q>), grid, dim3(256), 0, s, x, XQ, M, K, Mp, Kp, units, inv);
+            } else {
+                if (vec) hipLaunchKernelGGL((tsg_transpose_quads_kernel<T, true, 8, Q>), grid, dim3(256), 0, s, x, XQ, M, K, Mp, Kp, units, inv);
+                else hipLaunchKernelGGL((tsg_transpose_quads_kernel<T, false, 8, Q>), grid, dim3(256), 0, s, x, XQ, M, K, Mp, Kp, units, inv);
+            }
+            return hipGetLastError() == hipSuccess ? 0 : -1;
+        });
+    });
+}
+
+// The row pass of an actquant call: inv and deq (float[M] each) of every row,
+// deq also to out when given, and with q8 the int8 q of the whole X (the
+// small-M walks).  An int8 X is refused (-1).
+int launch_row_absmax(const void *X, int xtype, int M, int K, float *inv, float *deq, float *out, int8_t *q8,
+                      void *stream)
+{
+    if (M <= 0) return 0;
+    if (xtype == kXI8) return -1;
+    hipStream_t s = (hipStream_t)stream;
+    const bool vec = K % 4 == 0 && x_quad_aligned(X, xtype);
+    const dim3 grid((unsigned)((M + 3) / 4));
+    return with_xtype(X, xtype, [&](auto *x) {
+        using T = std::remove_cv_t<std::remove_pointer_t<decltype(x)>>;
+        if constexpr (std::is_same_v<T, xi8>) {
+            return -1;
         } else {
-            if (vec) hipLaunchKernelGGL((tsg_transpose_quads_kernel<T, true, 8>), grid, dim3(256), 0, s, x, XQ, M, K, Mp, Kp, units);
-            else hipLaunchKernelGGL((tsg_transpose_quads_kernel<T, false, 8>), grid, dim3(256), 0, s, x, XQ, M, K, Mp, Kp, units);
+            if (q8) {
+                if (vec) hipLaunchKernelGGL((tsg_row_absmax_kernel<T, true, true>), grid, dim3(256), 0, s, x, M, K, inv, deq, out, q8);
+                else hipLaunchKernelGGL((tsg_row_absmax_kernel<T, false, true>), grid, dim3(256), 0, s, x, M, K, inv, deq, out, q8);
+            } else {
+                if (vec) hipLaunchKernelGGL((tsg_row_absmax_kernel<T, true, false>), grid, dim3(256), 0, s, x, M, K, inv, deq, out, q8);
+                else hipLaunchKernelGGL((tsg_row_absmax_kernel<T, false, false>), grid, dim3(256), 0, s, x, M, K, inv, deq, out, q8);
+            }
+            return hipGetLastError() == hipSuccess ? 0 : -1;
         }
-        return hipGetLastError() == hipSuccess ? 0 : -1;
     });
 }
 

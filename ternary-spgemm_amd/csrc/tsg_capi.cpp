@@ -84,6 +84,14 @@ struct tsg_tcsc {
     hipStream_t work_stream = nullptr;
     hipEvent_t work_ev = nullptr;
     bool work_used = false;
+    // scratch of the actquant calls (tsg_actquant.h): inv at d_aq[0, aq_rows),
+    // deq at d_aq[aq_rows, 2 aq_rows), and the int8 q (M x K) of a call that
+    // runs a small-M walk.  Grow-only and shared by every stream like d_work:
+    // the same event orders its reuse (work_begin / work_end)
+    float *d_aq = nullptr;
+    size_t aq_rows = 0;
+    int8_t *d_aq8 = nullptr;
+    size_t aq8_bytes = 0;
     // host-pointer path staging (tcsc_hip_gemm): grow-only
     float *d_x = nullptr, *d_b = nullptr, *d_y = nullptr, *d_alpha = nullptr;
     size_t x_bytes = 0, y_bytes = 0;
@@ -164,6 +172,35 @@ int ensure_work(tsg_tcsc *h, int M, int tile_m, int chunk, bool capturing)
     if (hipMalloc(&h->d_work, need) != hipSuccess)
         return fail(TSG_ERR_NOMEM, "hipMalloc of " + std::to_string(need) + " B work buffer failed");
     h->work_bytes = need;
+    return TSG_OK;
+}
+
+// Grows the actquant scratch (grow-only, the rules of ensure_work): `rows`
+// row scales of each kind, q8 bytes of int8 q.
+int ensure_aq(tsg_tcsc *h, int rows, size_t q8, bool capturing)
+{
+    const size_t need = ((size_t)std::max(rows, 1) + 127) / 128 * 128;
+    if (need <= h->aq_rows && q8 <= h->aq8_bytes) return TSG_OK;
+    if (capturing)
+        return fail(TSG_ERR_ARG, "M=" + std::to_string(rows) + " needs a larger activation-quantisation scratch "
+                                 "during stream capture; call tcsc_hip_reserve(h, max_M) before capturing");
+    if (h->d_aq || h->d_aq8) HIP_TRY(hipDeviceSynchronize());  // launches that may still read the old buffers
+    if (need > h->aq_rows) {
+        if (h->d_aq) HIP_TRY(hipFree(h->d_aq));
+        h->d_aq = nullptr;
+        h->aq_rows = 0;
+        if (hipMalloc(&h->d_aq, 2 * need * sizeof(float)) != hipSuccess)
+            return fail(TSG_ERR_NOMEM, "hipMalloc of the activation-quantisation scales failed");
+        h->aq_rows = need;
+    }
+    if (q8 > h->aq8_bytes) {
+        if (h->d_aq8) HIP_TRY(hipFree(h->d_aq8));
+        h->d_aq8 = nullptr;
+        h->aq8_bytes = 0;
+        if (hipMalloc(&h->d_aq8, q8) != hipSuccess)
+            return fail(TSG_ERR_NOMEM, "hipMalloc of " + std::to_string(q8) + " B of quantised activations failed");
+        h->aq8_bytes = q8;
+    }
     return TSG_OK;
 }
 
@@ -407,6 +444,11 @@ struct Call {
     int M;
     hipStream_t s;
     bool prelu, capturing;
+    // an actquant call (tsg_actquant.h): X is quantised per row on the way in,
+    // drs is the scratch's deq (set by the launch functions), drs_out the
+    // caller's copy of it (may be null)
+    bool quant = false;
+    float *drs_out = nullptr;
 };
 
 // Before a call stages its X^T: the work buffer holds it (ensure_work), and
@@ -414,7 +456,10 @@ struct Call {
 // stream: this call's staging waits for it (same stream: stream order)
 int work_begin(tsg_tcsc *h, const CallPlan &p, const Call &c)
 {
-    const int rc = ensure_work(h, c.M, p.tile_m, p.chunk, c.capturing);
+    // (a walk has no X^T: it comes here for the actquant scratch alone)
+    int rc = p.is_ell() ? TSG_OK : ensure_work(h, c.M, p.tile_m, p.chunk, c.capturing);
+    if (!rc && c.quant)
+        rc = ensure_aq(h, c.M, p.is_ell() ? std::max<size_t>((size_t)c.M * h->plan.K, 16) : 0, c.capturing);
     if (rc) return rc;
     if (!c.capturing && h->work_used && h->work_stream != c.s) HIP_TRY(hipStreamWaitEvent(c.s, h->work_ev, 0));
     return TSG_OK;
@@ -435,15 +480,36 @@ int work_end(tsg_tcsc *h, const Call &c)
     return TSG_OK;
 }
 
+// The row pass of an actquant call, after work_begin: inv and deq of every row
+// into the scratch (and deq to the caller), for a walk also the int8 q
+int quant_rows(tsg_tcsc *h, const Call &c, bool q8)
+{
+    if (tsg::launch_row_absmax(c.dX, c.xtype, c.M, h->plan.K, h->d_aq, h->d_aq + h->aq_rows, c.drs_out,
+                               q8 ? h->d_aq8 : nullptr, c.s) != 0)
+        return fail(TSG_ERR_HIP, std::string("row pass launch: ") + hipGetErrorString(hipGetLastError()));
+    return TSG_OK;
+}
+
 // small M: the ELL walk reads X in place, whatever its element type (no X^T
 // staging, no work buffer)
-int run_ell(tsg_tcsc *h, const CallPlan &p, const Call &c)
+int run_ell(tsg_tcsc *h, const CallPlan &p, const Call &c0)
 {
-    if (!h->ell[p.ell].ready && c.capturing)
-        return fail(TSG_ERR_ARG, "M=" + std::to_string(c.M) + " runs the small-M kernel, whose image is not "
+    if (!h->ell[p.ell].ready && c0.capturing)
+        return fail(TSG_ERR_ARG, "M=" + std::to_string(c0.M) + " runs the small-M kernel, whose image is not "
                                  "built yet; call tcsc_hip_reserve before capturing");
     int rc = ensure_ell(h, p.ell);
     if (rc) return rc;
+    // an actquant call: the row pass writes q as int8 into the scratch, and the
+    // walk runs on it as an int8-X call scaled by the scratch's deq
+    Call c = c0;
+    if (c.quant) {
+        rc = work_begin(h, p, c);
+        if (!rc) rc = quant_rows(h, c, true);
+        if (rc) return rc;
+        c.dX = h->d_aq8;
+        c.xtype = tsg::kXI8;
+        c.drs = h->d_aq + h->aq_rows;
+    }
     int slot;
     rc = timing_begin(h, c.capturing, c.s, slot);
     if (rc) return rc;
@@ -456,7 +522,8 @@ int run_ell(tsg_tcsc *h, const CallPlan &p, const Call &c)
                                                c.M,                                               N, K, e.img.C, e.img.nch, e.img.xb, e.img.zr, c.prelu ? 1 : 0, c.s);
     if (lrc != 0)
         return fail(TSG_ERR_HIP, std::string("small-M kernel launch: ") + hipGetErrorString(hipGetLastError()));
-    return timing_end(h, slot, c.s);
+    rc = timing_end(h, slot, c.s);
+    return rc || !c.quant ? rc : work_end(h, c);
 }
 
 // the register-X walk: X^T pass, then the kernel
@@ -465,17 +532,20 @@ int run_rx(tsg_tcsc *h, const CallPlan &p, const Call &c)
     const int N = h->plan.N, K = h->plan.K;
     const XtDims d = dims_for(c.M, K, p.tile_m, p.chunk);
     int rc = work_begin(h, p, c);
+    if (!rc && c.quant) rc = quant_rows(h, c, false);
     if (rc) return rc;
+    const float *inv = c.quant ? h->d_aq : nullptr;
+    const float *drs = c.quant ? h->d_aq + h->aq_rows : c.drs;
     if (K == 0) {
         // no X at all: chain is +0; X^T stays zero
         HIP_TRY(hipMemsetAsync(h->d_work, 0, (size_t)d.Mp * d.Kp * sizeof(float), c.s));
-    } else if (tsg::launch_transpose(c.dX, c.xtype, h->d_work, c.M, K, d.Mp, d.Kp, c.s) != 0) {
+    } else if (tsg::launch_transpose(c.dX, c.xtype, h->d_work, c.M, K, d.Mp, d.Kp, c.s, inv) != 0) {
         return fail(TSG_ERR_HIP, std::string("transpose launch: ") + hipGetErrorString(hipGetLastError()));
     }
     int slot;
     rc = timing_begin(h, c.capturing, c.s, slot);
     if (rc) return rc;
-    if (tsg::launch_tcsc_rx(h->d_work, d.Mp, h->d_seg, h->d_ent, c.db, c.dalpha, c.drs, c.dcs, c.dY, c.ytype, c.ldY, c.M, N,
+    if (tsg::launch_tcsc_rx(h->d_work, d.Mp, h->d_seg, h->d_ent, c.db, c.dalpha, drs, c.dcs, c.dY, c.ytype, c.ldY, c.M, N,
                             h->rimg.Npad, h->rimg.nch, c.prelu ? 1 : 0, c.s) != 0)
         return fail(TSG_ERR_HIP, std::string("tcsc launch: ") + hipGetErrorString(hipGetLastError()));
     rc = timing_end(h, slot, c.s);
@@ -500,7 +570,8 @@ int run_jit(tsg_tcsc *h, const CallPlan &p, const tsg_tcsc::JitVariant &jv, cons
     // (the image's DMA reads fp32: an X of another type is always staged, by
     // the pass that widens it -- also at shapes where an fp32 X needs no work
     // buffer, which tcsc_hip_reserve sizes for the staged copy regardless)
-    const bool direct = c.xtype == tsg::kXF32 &&
+    // (an actquant call is staged too: its staging pass quantises)
+    const bool direct = !c.quant && c.xtype == tsg::kXF32 &&
                         tsg::x_direct(h->plan, p.shape, jv.piece_rows, ((uintptr_t)c.dX & 15) == 0, c.M);
     if (r64 && jv.chunk != p.chunk)  // the image and this call's X^T dims must agree (TSG_JIT_QBLOCK read at both)
         return fail(TSG_ERR_ARG, "64-row image built for " + std::to_string(jv.chunk) + "-row chunks, call expects " +
@@ -511,15 +582,21 @@ int run_jit(tsg_tcsc *h, const CallPlan &p, const tsg_tcsc::JitVariant &jv, cons
                             ? 4 * ((jv.nch - 1) * tsg::kJit64RowChunk - tsg::jit64_row_kbase(K, jv.nch, jv.nch - 1))
                             : 0;
     int rc;
+    const float *inv = nullptr, *drs = c.drs;
     if (!direct) {  // (direct: no staging kernel, the dispatcher's DMA reads X itself)
         rc = work_begin(h, p, c);
+        if (!rc && c.quant) rc = quant_rows(h, c, false);
         if (rc) return rc;
+        if (c.quant) {
+            inv = h->d_aq;
+            drs = h->d_aq + h->aq_rows;
+        }
         if (K == 0) {
             // no X at all: chain is +0; X^T stays zero
             HIP_TRY(hipMemsetAsync(h->d_work, 0, (size_t)d.Mp * d.Kp * sizeof(float), c.s));
         } else if ((r64 ? tsg::launch_transpose_quads(c.dX, c.xtype, h->d_work, c.M, K, d.Mp, d.Kp, jv.piece_rows, c.s,
-                                                      p.chunk)
-                        : tsg::launch_transpose_pairs(c.dX, c.xtype, h->d_work, c.M, K, d.Mp, d.Kp, c.s)) != 0) {
+                                                      p.chunk, inv)
+                        : tsg::launch_transpose_pairs(c.dX, c.xtype, h->d_work, c.M, K, d.Mp, d.Kp, c.s, inv)) != 0) {
             return fail(TSG_ERR_HIP, std::string("transpose launch: ") + hipGetErrorString(hipGetLastError()));
         }
     }
@@ -527,7 +604,7 @@ int run_jit(tsg_tcsc *h, const CallPlan &p, const tsg_tcsc::JitVariant &jv, cons
     rc = timing_begin(h, c.capturing, c.s, slot);
     if (rc) return rc;
     if (tsg::launch_tcsc_jit(jv.mod, direct ? static_cast<const float *>(c.dX) : h->d_work, d.Mp, jv.d_wcode, c.db,
-                             c.dalpha, c.drs, c.dcs, c.dY, c.ytype, c.ldY, c.M, N,
+                             c.dalpha, drs, c.dcs, c.dY, c.ytype, c.ldY, c.M, N,
                              jv.Npad, jv.nch, c.prelu ? 1 : 0, h->d_status, jv.nw * jv.waves, waves, p.gn, p.gm, p.tmask,
                              c.s, p.tile_m, direct ? K : 0, lastadj, p.xtouch, p.tnear) != 0)
         return fail(TSG_ERR_HIP, std::string("tcsc launch: ") + hipGetErrorString(hipGetLastError()));
@@ -538,9 +615,12 @@ int run_jit(tsg_tcsc *h, const CallPlan &p, const tsg_tcsc::JitVariant &jv, cons
 
 int run_dev(tsg_tcsc *h, const void *dX, const float *db, const float *dalpha, void *dY, int64_t ldY, int M,
             int N, int K, hipStream_t s, bool prelu, int xtype = tsg::kXF32, int ytype = tsg::kYF32,
-            const float *drs = nullptr, const float *dcs = nullptr)
+            const float *drs = nullptr, const float *dcs = nullptr, bool quant = false, float *drs_out = nullptr)
 {
     if (!h) return fail(TSG_ERR_ARG, "null handle");
+    if (quant && xtype == tsg::kXI8)  // refused before anything is enqueued
+        return fail(TSG_ERR_ARG, "xtype=3 (int8): the actquant calls quantise an fp32, fp16 or bf16 X; an int8 X "
+                                 "goes to tcsc_hip_gemm_dev_scaled with its own scale");
     if (!tsg::xtype_ok(xtype))  // refused before anything is enqueued
         return fail(TSG_ERR_ARG,
                     "xtype=" + std::to_string(xtype) + " is not a tsg_xtype (0 fp32, 1 fp16, 2 bf16, 3 int8)");
@@ -562,7 +642,8 @@ int run_dev(tsg_tcsc *h, const void *dX, const float *db, const float *dalpha, v
     std::lock_guard<std::mutex> lk(h->mu);
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     HIP_TRY(hipStreamIsCapturing(s, &cap));
-    const Call c{dX, xtype, db, dalpha, drs, dcs, dY, ytype, ldY, M, s, prelu, cap != hipStreamCaptureStatusNone};
+    const Call c{dX, xtype, db, dalpha, drs, dcs, dY, ytype, ldY, M, s, prelu, cap != hipStreamCaptureStatusNone,
+                 quant, drs_out};
     CallPlan p = tsg::plan_call(h->plan, M);
     if (p.is_ell()) return run_ell(h, p, c);
     if (!p.is_jit()) return run_rx(h, p, c);
@@ -744,7 +825,8 @@ void free_handle(tsg_tcsc *h)
     if (h->ring_count) (void)hipDeviceSynchronize();
     if (h->work_ev) (void)hipEventDestroy(h->work_ev);
     for (void *p : {(void *)h->d_seg, (void *)h->d_ent, (void *)h->d_work, (void *)h->d_x,
-                    (void *)h->d_b, (void *)h->d_y, (void *)h->d_alpha, (void *)h->d_status})
+                    (void *)h->d_b, (void *)h->d_y, (void *)h->d_alpha, (void *)h->d_status, (void *)h->d_aq,
+                    (void *)h->d_aq8})
         if (p) (void)hipFree(p);
     for (auto *vs : {&h->jv[0], &h->jv64[0], &h->jv64h[0]})
         for (size_t i = 0; i < (vs == &h->jv[0] ? std::size(h->jv) : vs == &h->jv64[0] ? std::size(h->jv64)
@@ -1028,8 +1110,15 @@ extern "C" int tcsc_hip_reserve(tsg_tcsc *h, int max_M)
     if (!h || max_M < 0) return fail(TSG_ERR_ARG, "bad reserve arguments");
     DeviceGuard g(h->device);
     std::lock_guard<std::mutex> lk(h->mu);
+    // the actquant scratch: the row scales of max_M rows, and the int8 q of the
+    // largest M <= max_M that runs a small-M walk
+    int walk_m = 0;
+    for (int m = std::max(max_M, 1); m >= 1 && !walk_m; m--)
+        if (tsg::plan_call(h->plan, m).is_ell()) walk_m = m;
+    int rc = ensure_aq(h, max_M, walk_m ? std::max<size_t>((size_t)walk_m * h->plan.K, 16) : 0, false);
+    if (rc) return rc;
     if (!h->plan.jit) return ensure_work(h, max_M, tsg::kRxTileM, tsg::kRxChunk, false);
-    int rc = ensure_work(h, max_M, tsg::kJitTileM, tsg::kJitChunk, false);
+    rc = ensure_work(h, max_M, tsg::kJitTileM, tsg::kJitChunk, false);
     // the 64-row image's k-quad X^T (same bytes or fewer)
     if (!rc) rc = ensure_work(h, max_M, tsg::kJit64TileM, tsg::jit64_chunk(false), false);
     if (rc) return rc;
@@ -1336,6 +1425,25 @@ extern "C" int tcsc_hip_gemm_prelu_dev_scaled(tsg_tcsc *h, const void *dX, int x
 {
     return run_dev(h, dX, db, dalpha, dY, ldY, M, N, K, (hipStream_t)stream, true, xtype, ytype, drow_scale,
                    dcol_scale);
+}
+
+// Fused per-row int8 activation quantisation (tsg_actquant.h): the _scaled
+// calls on q = quantised X with drow_scale = deq, both made here -- the row
+// pass finds deq, the staging pass quantises (Call::quant, Call::drs_out)
+extern "C" int tcsc_hip_gemm_dev_actquant(tsg_tcsc *h, const void *dX, int xtype, float *drow_scale_out,
+                                          const float *dcol_scale, const float *db, void *dY, int ytype, int64_t ldY,
+                                          int M, int N, int K, void *stream)
+{
+    return run_dev(h, dX, db, nullptr, dY, ldY, M, N, K, (hipStream_t)stream, false, xtype, ytype, nullptr, dcol_scale,
+                   true, drow_scale_out);
+}
+
+extern "C" int tcsc_hip_gemm_prelu_dev_actquant(tsg_tcsc *h, const void *dX, int xtype, float *drow_scale_out,
+                                                const float *dcol_scale, const float *db, const float *dalpha,
+                                                void *dY, int ytype, int64_t ldY, int M, int N, int K, void *stream)
+{
+    return run_dev(h, dX, db, dalpha, dY, ldY, M, N, K, (hipStream_t)stream, true, xtype, ytype, nullptr, dcol_scale,
+                   true, drow_scale_out);
 }
 
 extern "C" int tcsc_hip_info(const tsg_tcsc *h, tsg_info *o)

@@ -52,6 +52,7 @@ EXPORTED_SYMBOLS = (
     "tcsc_hip_gemm_dev_x", "tcsc_hip_gemm_prelu_dev_x",
     "tcsc_hip_gemm_dev_xy", "tcsc_hip_gemm_prelu_dev_xy",
     "tcsc_hip_gemm_dev_scaled", "tcsc_hip_gemm_prelu_dev_scaled",
+    "tcsc_hip_gemm_dev_actquant", "tcsc_hip_gemm_prelu_dev_actquant",
 )
 
 # enum tsg_xtype (include/ternary_spgemm.h): element type of X on the _x calls
@@ -118,6 +119,10 @@ def lib() -> C.CDLL:
                                            C.c_int, vp]
     L.tcsc_hip_gemm_prelu_dev_scaled.argtypes = [H, vp, C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_int64, C.c_int,
                                                  C.c_int, C.c_int, vp]
+    L.tcsc_hip_gemm_dev_actquant.argtypes = [H, vp, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int64, C.c_int, C.c_int,
+                                             C.c_int, vp]
+    L.tcsc_hip_gemm_prelu_dev_actquant.argtypes = [H, vp, C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_int64, C.c_int,
+                                                   C.c_int, C.c_int, vp]
     L.tcsc_hip_reserve.argtypes = [H, C.c_int]
     L.tcsc_hip_info.argtypes = [H, C.POINTER(tsg_info)]
     L.tcsc_hip_to_dense.argtypes = [H, vp, C.c_int, C.c_int]
@@ -440,6 +445,25 @@ def gen_x(M: int, K: int, seed: int, rng: int = 512) -> np.ndarray:
     return X
 
 
+def act_quant_ref(Xw) -> Tuple[np.ndarray, np.ndarray]:
+    """The contract of the actquant calls (include/ternary_spgemm.h
+    tcsc_hip_gemm_dev_actquant) in numpy: per-row symmetric int8 quantisation
+    of the widened fp32 X [M, K], every operation fp32 and rounded once, ties
+    to even.  Returns (q int8 [M, K], deq float32 [M]); the call's Y is the
+    scaled call's on X = q with row_scale = deq."""
+    Xw = np.asarray(Xw)
+    if Xw.dtype != np.float32 or Xw.ndim != 2:
+        raise TSGError(1, "act_quant_ref", "Xw must be a float32 [M, K] array")
+    f = np.float32
+    amax = np.abs(Xw).max(axis=1) if Xw.shape[1] else np.zeros(Xw.shape[0], f)
+    a = np.maximum(amax, f(1e-5)).astype(f)
+    inv = (f(127.0) / a).astype(f)
+    deq = (a / f(127.0)).astype(f)
+    t = np.rint((Xw * inv[:, None]).astype(f))  # np.rint: half to even
+    q = np.minimum(np.maximum(t, f(-127.0)), f(127.0))
+    return q.astype(np.int8), deq
+
+
 class registered_host:
     """Context manager: page-locks numpy arrays for repeated host-pointer
     calls (tcsc_hip_host_register), unlocks them on exit."""
@@ -703,7 +727,39 @@ class TCSCDevice:
         return self._torch_xy("gemm_torch_scaled", X, b, Y, alpha, out_dtype, narrow_y=True, scaled=True,
                               row_scale=row_scale, col_scale=col_scale)
 
-    def _torch_xy(self, where, X, b, Y, alpha, out_dtype, narrow_y, scaled=False, row_scale=None, col_scale=None):
+    def gemm_dev_actquant(self, dX: int, xtype: int, db: int, dY: int, ytype: int, M: int, stream: int = 0,
+                          dalpha: Optional[int] = None, ldY: Optional[int] = None,
+                          drow_scale_out: Optional[int] = None, dcol_scale: Optional[int] = None) -> None:
+        """gemm_dev_scaled with the int8 activations and their row scale made
+        inside the call (tcsc_hip_gemm_dev_actquant): dX is fp32, fp16 or bf16
+        (TSG_X_I8 is refused); each row is quantised to int8 by its own maximum
+        (act_quant_ref states the arithmetic) in the pass that stages X, and
+        Y = ((chain(q) * deq[m]) * dcol_scale[n]) + db[n] as on gemm_dev_scaled.
+        drow_scale_out: None or a device float[M] that receives deq."""
+        ld = self.N if ldY is None else int(ldY)
+        if dalpha is None:
+            _check(lib().tcsc_hip_gemm_dev_actquant(self._h, dX, int(xtype), drow_scale_out, dcol_scale, db, dY,
+                                                    int(ytype), ld, M, self.N, self.K, stream or None),
+                   "tcsc_hip_gemm_dev_actquant")
+        else:
+            _check(lib().tcsc_hip_gemm_prelu_dev_actquant(self._h, dX, int(xtype), drow_scale_out, dcol_scale, db,
+                                                          dalpha, dY, int(ytype), ld, M, self.N, self.K,
+                                                          stream or None), "tcsc_hip_gemm_prelu_dev_actquant")
+
+    def gemm_torch_actquant(self, X, b, Y=None, alpha=None, out_dtype=None, col_scale=None, row_scale_out=None):
+        """A W1.58A8 linear layer from activations in their own type: X is a
+        contiguous [M, K] float32, float16 or bfloat16 tensor on the handle's
+        device (int8 is refused: it has its scale, gemm_torch_scaled); every
+        row is quantised to int8 by its own maximum inside the call and the
+        result is gemm_torch_scaled(q, b, row_scale=deq, col_scale=col_scale)
+        bit for bit, (q, deq) = act_quant_ref(X.float()).  row_scale_out: None
+        or a contiguous float32 [M] tensor that receives deq.  b, alpha,
+        col_scale, Y and out_dtype as on gemm_torch_scaled.  Returns Y."""
+        return self._torch_xy("gemm_torch_actquant", X, b, Y, alpha, out_dtype, narrow_y=True, col_scale=col_scale,
+                              row_scale_out=row_scale_out, actquant=True)
+
+    def _torch_xy(self, where, X, b, Y, alpha, out_dtype, narrow_y, scaled=False, row_scale=None, col_scale=None,
+                  row_scale_out=None, actquant=False):
         import torch
         dev = torch.device("cuda", self.device)
         ytypes = {torch.float32: TSG_Y_F32}
@@ -720,11 +776,14 @@ class TCSCDevice:
             raise TSGError(1, where, f"X must be a contiguous float32, float16, bfloat16 or int8 "
                                               f"{[M, self.K]} tensor on {dev}, got {X.dtype} {list(X.shape)} on "
                                               f"{X.device}{'' if X.is_contiguous() else ' (non-contiguous)'}")
+        if actquant and X.dtype == torch.int8:
+            raise TSGError(1, where, "X must be float32, float16 or bfloat16: an int8 X is quantised already "
+                                     "(gemm_torch_scaled takes it with its row scale)")
         for name, t, shape in (("b", b, (self.N,)), ("alpha", alpha, (self.N,)), ("row_scale", row_scale, (M,)),
-                               ("col_scale", col_scale, (self.N,))):
+                               ("col_scale", col_scale, (self.N,)), ("row_scale_out", row_scale_out, (M,))):
             if t is None:
                 continue
-            if name.endswith("_scale") and not isinstance(t, torch.Tensor):
+            if "_scale" in name and not isinstance(t, torch.Tensor):
                 raise TSGError(1, where, f"{name} must be a tensor, got {type(t)}")
             if t.dtype != torch.float32 or t.device != dev or not t.is_contiguous() or tuple(t.shape) != shape:
                 raise TSGError(1, where, f"{name} must be a contiguous float32 {list(shape)} tensor on "
@@ -748,7 +807,12 @@ class TCSCDevice:
             raise TSGError(1, where, f"Y's rows overlap: stride(0) = {ldY} < N = {self.N}")
         stream = torch.cuda.current_stream(dev).cuda_stream
         dalpha = None if alpha is None else alpha.data_ptr()
-        if scaled:
+        if actquant:
+            self.gemm_dev_actquant(X.data_ptr(), xtypes[X.dtype], b.data_ptr(), Y.data_ptr(), ytypes[Y.dtype], M,
+                                   stream, dalpha, ldY=ldY,
+                                   drow_scale_out=None if row_scale_out is None else row_scale_out.data_ptr(),
+                                   dcol_scale=None if col_scale is None else col_scale.data_ptr())
+        elif scaled:
             self.gemm_dev_scaled(X.data_ptr(), xtypes[X.dtype], b.data_ptr(), Y.data_ptr(), ytypes[Y.dtype], M, stream,
                                  dalpha, ldY=ldY, drow_scale=None if row_scale is None else row_scale.data_ptr(),
                                  dcol_scale=None if col_scale is None else col_scale.data_ptr())
