@@ -335,7 +335,7 @@ int tcsc_hip_gemm_prelu_dev_scaled(tsg_tcsc *h, const void *dX, int xtype, const
  * As on _scaled: ldY, dY's alignment and the written-range guarantee, the
  * 16-bit neighbour in a shared dword included; stream semantics; isolation
  * from memory outside the operands and from earlier calls; the kernel and
- * image an M picks.  The scratch (two floats per row, and M * K bytes for a
+ * image an M picks.  The scratch (three floats per row, and M * K bytes for a
  * walk) is the handle's, grow-only and shared by every stream exactly like the
  * work buffer: tcsc_hip_reserve(h, max_M) sizes it, and a call that would grow
  * it during stream capture is TSG_ERR_ARG naming tcsc_hip_reserve.
@@ -347,6 +347,63 @@ int tcsc_hip_gemm_dev_actquant(tsg_tcsc *h, const void *dX, int xtype, float *dr
 int tcsc_hip_gemm_prelu_dev_actquant(tsg_tcsc *h, const void *dX, int xtype, float *drow_scale_out,
                                      const float *dcol_scale, const float *db, const float *dalpha, void *dY,
                                      int ytype, int64_t ldY, int M, int N, int K, void *stream);
+
+/* The _actquant calls with the RMSNorm that stands in front of the activation
+ * quantisation of a BitNet-style layer made inside the call too:
+ * x -> x * rsqrt(mean(x^2) + eps) * gamma, then the per-row int8 quantisation,
+ * both fused into the passes that read X -- no normalised copy of X in memory.
+ *
+ * Contract.  All arithmetic is fp32 on the widened X (the widening is exact),
+ * every operation rounded once, no fma and no contraction anywhere, the
+ * division and the square root IEEE correctly rounded (no reciprocal-square-
+ * root shortcut):
+ *
+ *   sq[k]   = x[m, k] * x[m, k]
+ *   s[p]    = ((+0 + sq[p]) + sq[p + 256]) + sq[p + 512] ...   p = 0..255: 256
+ *             strided partial sums, each serial in ascending k
+ *   ss      = the 256 partials summed by a balanced binary tree, neighbours
+ *             first: eight times  s'[p] = s[2p] + s[2p + 1]
+ *   ms      = ss / (float)K
+ *   rn[m]   = 1.0f / sqrtf(ms + eps)
+ *   xn[m,k] = (x[m, k] * rn[m]) * gamma[k]      two roundings, in this order;
+ *             dgamma NULL: the second multiply is not performed
+ *   Y, deq  = what tcsc_hip_gemm_[prelu_]dev_actquant gives on the fp32 X = xn
+ *             with the same other arguments -- bit for bit.
+ *
+ * The shape of the sum is part of the contract because a sum of squares is not
+ * associative; an absent element adds nothing (the same as adding +0), and an
+ * aligned and a misaligned X give the same bits.
+ * eps must be finite and > 0: anything else is TSG_ERR_ARG with a message that
+ * names eps, nothing enqueued.  xtype is TSG_X_F32, TSG_X_F16 or TSG_X_BF16;
+ * TSG_X_I8 is refused as on _actquant.
+ * dgamma is float[K] of device memory that needs only 4-byte alignment (it may
+ * be a slice); it is never written, and nothing outside [dgamma, dgamma + K)
+ * reaches Y.
+ * K = 0: no sum and no division happen; the call is _actquant at K = 0 (Y = b,
+ * deq = 1e-5f / 127).  An all-zero row: rn = 1 / sqrtf(eps), xn = 0, q = 0,
+ * Y[m, :] = b.  A row that holds an inf or a NaN, or whose ss overflows: its
+ * own Y row and deq[m] are unspecified; nothing faults, and every other row is
+ * bit for bit what it is without it.
+ * How it runs.  The row pass of _actquant gains a sweep in front that
+ * accumulates the 256 partials, reduces them and computes rn; its maximum and,
+ * for a small-M walk, its int8 q are taken of xn; it stores rn next to inv and
+ * deq in the scratch (three floats per row).  The staging pass then stores
+ * q(xn) for each value it loads.  Always staged, no launch and no
+ * synchronisation over _actquant.
+ * drow_scale_out, dcol_scale, db, dalpha, ytype, ldY, the written-range
+ * guarantee, stream semantics, the kernel an M picks, isolation from earlier
+ * calls, the scratch's grow-only / tcsc_hip_reserve / capture rules: as on
+ * _actquant.
+ * Out of scope: a norm without the quantisation, LayerNorm (a mean), a 16-bit
+ * gamma, an rn output, the host-pointer calls, the plugin header.  Extension:
+ * no reference counterpart. */
+int tcsc_hip_gemm_dev_normquant(tsg_tcsc *h, const void *dX, int xtype, const float *dgamma, float eps,
+                                float *drow_scale_out, const float *dcol_scale, const float *db, void *dY,
+                                int ytype, int64_t ldY, int M, int N, int K, void *stream);
+int tcsc_hip_gemm_prelu_dev_normquant(tsg_tcsc *h, const void *dX, int xtype, const float *dgamma, float eps,
+                                      float *drow_scale_out, const float *dcol_scale, const float *db,
+                                      const float *dalpha, void *dY, int ytype, int64_t ldY, int M, int N, int K,
+                                      void *stream);
 
 /* Pre-allocates the per-handle work buffer for row counts up to max_M and, on
  * the weight-compiled kernel, compiles every code image a call with M <= max_M

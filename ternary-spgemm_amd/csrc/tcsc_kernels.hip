@@ -17,8 +17,10 @@
 // int8; they need X aligned to 4 elements and K % 4 == 0 (x_quad_aligned).
 // Every staging pass is also a template on Q: an actquant call's pass
 // quantises each value it loads, xquant(v, inv[m]) (tsg_actquant.h), with
-// inv[m] from tsg_row_absmax_kernel, the row pass that runs before it; Q =
-// false is the pass as it was.
+// inv[m] from tsg_row_absmax_kernel, the row pass that runs before it; a
+// normquant call's pass normalises first, xquant(xnorm(v, rn[m], g[k]), inv[m])
+// (tsg_norm.h), with rn[m] from the same row pass.  Q is an XStage; kStageNone
+// is the pass as it was.
 // tsg_tcsc_rx_kernel: the register-X walk, the fallback when a W is too large
 //   for one weight-compiled image (> ~300 M nonzeros on one handle) or the
 //   generated image cannot be loaded (tsg_capi.cpp create_impl).
@@ -28,6 +30,7 @@
 
 #include "tsg_actquant.h"
 #include "tsg_internal.h"
+#include "tsg_norm.h"
 #include "tsg_scale.h"
 #include "tsg_xtype.h"
 #include "tsg_ytype.h"
@@ -35,10 +38,11 @@
 namespace tsg {
 
 // ------------------------------------------------------------------ kernel 1 --
-template <typename T, bool Q>
+template <typename T, int Q>
 __global__ __launch_bounds__(256) void tsg_transpose_kernel(const T *__restrict__ X,
                                                             float *__restrict__ XT, int M, int K,
-                                                            int Mp, int Kp, const float *__restrict__ inv)
+                                                            int Mp, int Kp, const float *__restrict__ inv,
+                                                            const float *__restrict__ rn, const float *__restrict__ g)
 {
     __shared__ float tile[64][65];
     const int k0 = blockIdx.x * 64, m0 = blockIdx.y * 64;
@@ -47,7 +51,7 @@ __global__ __launch_bounds__(256) void tsg_transpose_kernel(const T *__restrict_
     for (int i = 0; i < 16; i++) {
         const int m = m0 + ty + 4 * i, k = k0 + tx;
         float v = (m < M && k < K) ? xload1(X + (size_t)m * K + k) : 0.0f;
-        if (Q && m < M) v = xquant(v, inv[m]);
+        if (Q && m < M) v = xstage<Q>(v, m, k, K, inv, rn, g);
         tile[ty + 4 * i][tx] = v;
     }
     __syncthreads();
@@ -61,10 +65,11 @@ __global__ __launch_bounds__(256) void tsg_transpose_kernel(const T *__restrict_
 // Same transpose with a quad per load and 16-byte stores (K % 4 == 0 and X
 // aligned to 4 elements): each lane loads 4 consecutive k of one m row and stores 4
 // consecutive m of one X^T row -- a quarter of the memory instructions.
-template <typename T, bool Q>
+template <typename T, int Q>
 __global__ __launch_bounds__(256) void tsg_transpose4_kernel(const T *__restrict__ X,
                                                              float *__restrict__ XT, int M, int K,
-                                                             int Mp, int Kp, const float *__restrict__ inv)
+                                                             int Mp, int Kp, const float *__restrict__ inv,
+                                                             const float *__restrict__ rn, const float *__restrict__ g)
 {
     __shared__ float tile[64][65];
     const int k0 = blockIdx.x * 64, m0 = blockIdx.y * 64;
@@ -75,7 +80,7 @@ __global__ __launch_bounds__(256) void tsg_transpose4_kernel(const T *__restrict
         float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         if (m < M && k < K) {
             v = xload4(X + (size_t)m * K + k);  // K % 4 == 0
-            if (Q) v = xquant4(v, inv[m]);
+            if (Q) v = xstage4<Q>(v, m, k, K, inv, rn, g);
         }
         tile[ml][c4] = v.x;
         tile[ml][c4 + 1] = v.y;
@@ -99,10 +104,11 @@ __global__ __launch_bounds__(256) void tsg_transpose4_kernel(const T *__restrict
 // VEC: K % 4 == 0 and X aligned to 4 elements), stores 16 B per lane, consecutive
 // lanes on consecutive mp (coalesced 512-B runs per pair row).  HBM-bound:
 // 8 * M * K bytes.
-template <typename T, bool VEC, bool Q>
+template <typename T, bool VEC, int Q>
 __global__ __launch_bounds__(256) void tsg_transpose_pairs_kernel(const T *__restrict__ X,
                                                                   float *__restrict__ XP, int M, int K,
-                                                                  int Mp, int Kp, const float *__restrict__ inv)
+                                                                  int Mp, int Kp, const float *__restrict__ inv,
+                                                                  const float *__restrict__ rn, const float *__restrict__ g)
 {
     __shared__ float tile[64][65];  // [m][k]
     const int k0 = blockIdx.x * 64, m0 = blockIdx.y * 64;
@@ -114,7 +120,7 @@ __global__ __launch_bounds__(256) void tsg_transpose_pairs_kernel(const T *__res
             float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
             if (m < M && k < K) {
             v = xload4(X + (size_t)m * K + k);  // K % 4 == 0
-            if (Q) v = xquant4(v, inv[m]);
+            if (Q) v = xstage4<Q>(v, m, k, K, inv, rn, g);
         }
             tile[ml][c4] = v.x;
             tile[ml][c4 + 1] = v.y;
@@ -127,7 +133,7 @@ __global__ __launch_bounds__(256) void tsg_transpose_pairs_kernel(const T *__res
         for (int i = 0; i < 16; i++) {
             const int m = m0 + ty + 4 * i, k = k0 + tx;
             float v = (m < M && k < K) ? xload1(X + (size_t)m * K + k) : 0.0f;
-            if (Q && m < M) v = xquant(v, inv[m]);
+            if (Q && m < M) v = xstage<Q>(v, m, k, K, inv, rn, g);
             tile[ty + 4 * i][tx] = v;
         }
     }
@@ -157,11 +163,12 @@ __global__ __launch_bounds__(256) void tsg_transpose_pairs_kernel(const T *__res
 // 128-B line is the next piece's, copied by the neighbouring workgroup); no
 // LDS, no barrier.  A workgroup copies 4 consecutive pieces of one (chunk, M
 // tile).  HBM-bound: 8 * Mp * Kp bytes.
-template <typename T, bool VEC, int PR, bool Q>
+template <typename T, bool VEC, int PR, int Q>
 __global__ __launch_bounds__(256) void tsg_transpose_quads_kernel(const T *__restrict__ X,
                                                                   float *__restrict__ XQ, int M, int K,
                                                                   int Mp, int Kp, int units,
-                                                                  const float *__restrict__ inv)
+                                                                  const float *__restrict__ inv,
+                                                                  const float *__restrict__ rn, const float *__restrict__ g)
 {
     // units: 1-KiB pieces per (chunk, M tile) -- 48, or 24 for the half ring
     constexpr int QP = 64 / PR;
@@ -188,7 +195,7 @@ __global__ __launch_bounds__(256) void tsg_transpose_quads_kernel(const T *__res
             if (k + 3 < K) v.w = xload1(row + k + 3);
         }
         // (a slot past K holds +0, and xquant(+0) is +0)
-        if (Q) v = xquant4(v, inv[m]);
+        if (Q) v = xstage4<Q>(v, m, k, K, inv, rn, g);
     }
     *reinterpret_cast<float4 *>(XQ + ((size_t)ct * units + pr) * 256 + (size_t)j * 4) = v;
 }
@@ -201,10 +208,11 @@ __global__ __launch_bounds__(256) void tsg_transpose_quads_kernel(const T *__res
 // of a row of X, so this is a gather-copy of row runs (no transpose): reads
 // and writes both run along rows.  Four workgroups per (chunk, M tile), 752
 // slots each.  HBM-bound: 2 * 4 * Mp * Kp bytes.
-template <typename T, bool VEC, bool Q>
+template <typename T, bool VEC, int Q>
 __global__ __launch_bounds__(256) void tsg_transpose_rows_kernel(const T *__restrict__ X,
                                                                  float *__restrict__ XR, int M, int K, int Mp,
-                                                                 int nch, const float *__restrict__ inv)
+                                                                 int nch, const float *__restrict__ inv,
+                                                                 const float *__restrict__ rn, const float *__restrict__ g)
 {
     constexpr int kQ = 47, kSlots = 64 * kQ, kPer = kSlots / 4;  // 752 slots per workgroup
     const int Mt = Mp >> 6;
@@ -228,7 +236,7 @@ __global__ __launch_bounds__(256) void tsg_transpose_rows_kernel(const T *__rest
                 if (k + 2 < K) v.z = xload1(row + k + 2);
                 if (k + 3 < K) v.w = xload1(row + k + 3);
             }
-            if (Q) v = xquant4(v, inv[m]);
+            if (Q) v = xstage4<Q>(v, m, k, K, inv, rn, g);
         }
         *reinterpret_cast<float4 *>(dst + (size_t)slot * 4) = v;
     }
@@ -244,23 +252,74 @@ __global__ __launch_bounds__(256) void tsg_transpose_rows_kernel(const T *__rest
 // reads its elements again (still in cache) and stores q as int8, row-major
 // [M][K], four per store when VEC (q8 is aligned to 4 B and K % 4 == 0); the
 // walk runs on q8 as an int8-X scaled call.  K = 0: no loads, amax = 0.
-template <typename T, bool VEC, bool Q8>
+// NORM: the row pass of a normquant call (tsg_norm.h).  A sweep in front
+// accumulates the row's 256 strided partial sums of squares -- with quad loads
+// lane l holds partials 4l .. 4l + 3, with scalar loads partials l + 64 j, j =
+// 0..3 -- and reduces them by the contract's tree, neighbours first: the in-lane
+// adds are levels 0 and 1 and the xor butterfly over lanes 1, 2, .., 32 levels 2
+// to 7 (quads), or the butterfly on each accumulator levels 0 to 5 and (j0 + j1)
+// + (j2 + j3) levels 6 and 7 (scalars).  An absent element adds nothing, so
+// both give the same bits.  The maximum and q are then taken of xn = xnorm(x,
+// rn, g[k]), and lane 0 also stores rn[m].  K = 0: no sum, no division.
+template <typename T, bool VEC, bool Q8, bool NORM>
 __global__ __launch_bounds__(256) void tsg_row_absmax_kernel(const T *__restrict__ X, int M, int K,
                                                              float *__restrict__ inv, float *__restrict__ deq,
-                                                             float *__restrict__ out, int8_t *__restrict__ q8)
+                                                             float *__restrict__ out, int8_t *__restrict__ q8,
+                                                             float *__restrict__ rnorm, const float *__restrict__ g,
+                                                             float eps)
 {
     const int lane = threadIdx.x & 63;
     const int m = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (m >= M) return;  // (whole waves: no barrier follows)
     const T *row = X + (size_t)m * K;
+    float rn = 0.0f;
+    if (NORM && K > 0) {
+        float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f, ss;
+        if (VEC) {
+            for (int k = 4 * lane; k < K; k += 256) {
+                const float4 v = xload4(row + k);
+                s0 = norm_sq_add(s0, v.x);
+                s1 = norm_sq_add(s1, v.y);
+                s2 = norm_sq_add(s2, v.z);
+                s3 = norm_sq_add(s3, v.w);
+            }
+            ss = (s0 + s1) + (s2 + s3);
+#pragma unroll
+            for (int d = 1; d <= 32; d <<= 1) ss = ss + __shfl_xor(ss, d, 64);
+        } else {
+            for (int k = lane; k < K; k += 256) {
+                s0 = norm_sq_add(s0, xload1(row + k));
+                if (k + 64 < K) s1 = norm_sq_add(s1, xload1(row + k + 64));
+                if (k + 128 < K) s2 = norm_sq_add(s2, xload1(row + k + 128));
+                if (k + 192 < K) s3 = norm_sq_add(s3, xload1(row + k + 192));
+            }
+#pragma unroll
+            for (int d = 1; d <= 32; d <<= 1) {
+                s0 = s0 + __shfl_xor(s0, d, 64);
+                s1 = s1 + __shfl_xor(s1, d, 64);
+                s2 = s2 + __shfl_xor(s2, d, 64);
+                s3 = s3 + __shfl_xor(s3, d, 64);
+            }
+            ss = (s0 + s1) + (s2 + s3);
+        }
+        rn = norm_rn(ss, K, eps);
+    }
     float amax = 0.0f;
     if (VEC) {
         for (int k = 4 * lane; k < K; k += 256) {
-            const float4 v = xload4(row + k);
+            float4 v = xload4(row + k);
+            if (NORM) {
+                const float4 gv = gload4(g, k, K);
+                v = make_float4(xnorm(v.x, rn, gv.x), xnorm(v.y, rn, gv.y), xnorm(v.z, rn, gv.z), xnorm(v.w, rn, gv.w));
+            }
             amax = fmaxf(amax, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
         }
     } else {
-        for (int k = lane; k < K; k += 64) amax = fmaxf(amax, fabsf(xload1(row + k)));
+        for (int k = lane; k < K; k += 64) {
+            float v = xload1(row + k);
+            if (NORM) v = xnorm(v, rn, gload1(g, k, K));
+            amax = fmaxf(amax, fabsf(v));
+        }
     }
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) amax = fmaxf(amax, __shfl_xor(amax, d, 64));
@@ -270,18 +329,29 @@ __global__ __launch_bounds__(256) void tsg_row_absmax_kernel(const T *__restrict
         inv[m] = iv;
         deq[m] = dq;
         if (out) out[m] = dq;
+        if (NORM) rnorm[m] = rn;
     }
     if (Q8) {
         int8_t *qrow = q8 + (size_t)m * K;
         if (VEC) {
             for (int k = 4 * lane; k < K; k += 256) {
-                const float4 v = xquant4(xload4(row + k), iv);
+                float4 v = xload4(row + k);
+                if (NORM) {
+                    const float4 gv = gload4(g, k, K);
+                    v = make_float4(xnormquant(v.x, rn, gv.x, iv), xnormquant(v.y, rn, gv.y, iv),
+                                    xnormquant(v.z, rn, gv.z, iv), xnormquant(v.w, rn, gv.w, iv));
+                } else {
+                    v = xquant4(v, iv);
+                }
                 const uint32_t w = ((uint32_t)(int)v.x & 0xffu) | (((uint32_t)(int)v.y & 0xffu) << 8) |
                                    (((uint32_t)(int)v.z & 0xffu) << 16) | ((uint32_t)(int)v.w << 24);
                 *reinterpret_cast<uint32_t *>(qrow + k) = w;
             }
         } else {
-            for (int k = lane; k < K; k += 64) qrow[k] = (int8_t)(int)xquant(xload1(row + k), iv);
+            for (int k = lane; k < K; k += 64) {
+                const float v = xload1(row + k);
+                qrow[k] = (int8_t)(int)(NORM ? xnormquant(v, rn, gload1(g, k, K), iv) : xquant(v, iv));
+            }
         }
     }
 }
@@ -478,34 +548,36 @@ __global__ __launch_bounds__(kRxWaves * 64, 8 / kRxWaves) void tsg_tcsc_rx_kerne
 }
 
 // ---------------------------------------------------------------- launchers --
-// Calls f(std::bool_constant<Q>) with Q = whether the staging pass quantises
-// (inv given, tsg_actquant.h).  An int8 X is never quantised (the C-ABI
-// refuses it), so that combination is not instantiated.
+// Calls f(std::integral_constant<int, Q>) with Q = what the staging pass does
+// to the values it loads (XStage, tsg_norm.h): quantise when inv is given,
+// normalise first when rn is given too.  An int8 X is never quantised (the
+// C-ABI refuses it), so those combinations are not instantiated.
 template <typename T, typename F>
-int with_quant(const float *inv, F &&f)
+int with_quant(const float *inv, const float *rn, F &&f)
 {
     if constexpr (std::is_same_v<T, xi8>) {
-        return inv ? -1 : f(std::false_type{});
+        return inv ? -1 : f(std::integral_constant<int, kStageNone>{});
     } else {
-        return inv ? f(std::true_type{}) : f(std::false_type{});
+        if (!inv) return f(std::integral_constant<int, kStageNone>{});
+        return rn ? f(std::integral_constant<int, kStageNorm>{}) : f(std::integral_constant<int, kStageQuant>{});
     }
 }
 
 int launch_transpose(const void *X, int xtype, float *XT, int M, int K, int Mp, int Kp, void *stream,
-                     const float *inv)
+                     const float *inv, const float *rn, const float *g)
 {
     dim3 grid((unsigned)((Kp + 63) / 64), (unsigned)(Mp / 64));
     const bool vec = K % 4 == 0 && x_quad_aligned(X, xtype);
     return with_xtype(X, xtype, [&](auto *x) {
         using T = std::remove_cv_t<std::remove_pointer_t<decltype(x)>>;
-        return with_quant<T>(inv, [&](auto q) {
-            constexpr bool Q = decltype(q)::value;
+        return with_quant<T>(inv, rn, [&](auto q) {
+            constexpr int Q = decltype(q)::value;
             if (vec)
                 hipLaunchKernelGGL((tsg_transpose4_kernel<T, Q>), grid, dim3(256), 0, (hipStream_t)stream, x, XT, M, K,
-                                   Mp, Kp, inv);
+                                   Mp, Kp, inv, rn, g);
             else
                 hipLaunchKernelGGL((tsg_transpose_kernel<T, Q>), grid, dim3(256), 0, (hipStream_t)stream, x, XT, M, K,
-                                   Mp, Kp, inv);
+                                   Mp, Kp, inv, rn, g);
             return hipGetLastError() == hipSuccess ? 0 : -1;
         });
     });
@@ -513,7 +585,7 @@ int launch_transpose(const void *X, int xtype, float *XT, int M, int K, int Mp, 
 
 
 int launch_transpose_pairs(const void *X, int xtype, float *XP, int M, int K, int Mp, int Kp, void *stream,
-                           const float *inv)
+                           const float *inv, const float *rn, const float *g)
 {
     // Mp is a multiple of 128 (the jit M tile) and Kp of 96: the 64 x 64 tiles
     // cover [0, Kp) x [0, Mp) exactly in m and up to 32 pad rows in k
@@ -521,21 +593,21 @@ int launch_transpose_pairs(const void *X, int xtype, float *XP, int M, int K, in
     const bool vec = K % 4 == 0 && x_quad_aligned(X, xtype);
     return with_xtype(X, xtype, [&](auto *x) {
         using T = std::remove_cv_t<std::remove_pointer_t<decltype(x)>>;
-        return with_quant<T>(inv, [&](auto q) {
-            constexpr bool Q = decltype(q)::value;
+        return with_quant<T>(inv, rn, [&](auto q) {
+            constexpr int Q = decltype(q)::value;
             if (vec)
                 hipLaunchKernelGGL((tsg_transpose_pairs_kernel<T, true, Q>), grid, dim3(256), 0, (hipStream_t)stream, x,
-                                   XP, M, K, Mp, Kp, inv);
+                                   XP, M, K, Mp, Kp, inv, rn, g);
             else
                 hipLaunchKernelGGL((tsg_transpose_pairs_kernel<T, false, Q>), grid, dim3(256), 0, (hipStream_t)stream,
-                                   x, XP, M, K, Mp, Kp, inv);
+                                   x, XP, M, K, Mp, Kp, inv, rn, g);
             return hipGetLastError() == hipSuccess ? 0 : -1;
         });
     });
 }
 
 int launch_transpose_quads(const void *X, int xtype, float *XQ, int M, int K, int Mp, int Kp, int piece_rows,
-                           void *stream, int chunk, const float *inv)
+                           void *stream, int chunk, const float *inv, const float *rn, const float *g)
 {
     hipStream_t s = (hipStream_t)stream;
     const bool vec = K % 4 == 0 && x_quad_aligned(X, xtype);
@@ -546,10 +618,10 @@ int launch_transpose_quads(const void *X, int xtype, float *XQ, int M, int K, in
         if (blocks >= ((int64_t)1 << 31)) return -1;
         return with_xtype(X, xtype, [&](auto *x) {
             using T = std::remove_cv_t<std::remove_pointer_t<decltype(x)>>;
-            return with_quant<T>(inv, [&](auto q) {
-                constexpr bool Q = decltype(q)::value;
-                if (vec) hipLaunchKernelGGL((tsg_transpose_rows_kernel<T, true, Q>), dim3((unsigned)blocks), dim3(256), 0, s, x, XQ, M, K, Mp, nch, inv);
-                else hipLaunchKernelGGL((tsg_transpose_rows_kernel<T, false, Q>), dim3((unsigned)blocks), dim3(256), 0, s, x, XQ, M, K, Mp, nch, inv);
+            return with_quant<T>(inv, rn, [&](auto q) {
+                constexpr int Q = decltype(q)::value;
+                if (vec) hipLaunchKernelGGL((tsg_transpose_rows_kernel<T, true, Q>), dim3((unsigned)blocks), dim3(256), 0, s, x, XQ, M, K, Mp, nch, inv, rn, g);
+                else hipLaunchKernelGGL((tsg_transpose_rows_kernel<T, false, Q>), dim3((unsigned)blocks), dim3(256), 0, s, x, XQ, M, K, Mp, nch, inv, rn, g);
                 return hipGetLastError() == hipSuccess ? 0 : -1;
             });
         });
@@ -565,14 +637,14 @@ int launch_transpose_quads(const void *X, int xtype, float *XQ, int M, int K, in
     dim3 grid((unsigned)blocks);
     return with_xtype(X, xtype, [&](auto *x) {
         using T = std::remove_cv_t<std::remove_pointer_t<decltype(x)>>;
-        return with_quant<T>(inv, [&](auto q) {
-            constexpr bool Q = decltype(q)::value;
+        return with_quant<T>(inv, rn, [&](auto q) {
+            constexpr int Q = decltype(q)::value;
             if (piece_rows == 16) {
-                if (vec) hipLaunchKernelGGL((tsg_transpose_quads_kernel<T, true, 16, Q>), grid, dim3(256), 0, s, x, XQ, M, K, Mp, Kp, units, inv);
-                else hipLaunchKernelGGL((tsg_transpose_quads_kernel<T, false, 16, Q>), grid, dim3(256), 0, s, x, XQ, M, K, Mp, Kp, units, inv);
+                if (vec) hipLaunchKernelGGL((tsg_transpose_quads_kernel<T, true, 16, Q>), grid, dim3(256), 0, s, x, XQ, M, K, Mp, Kp, units, inv, rn, g);
+                else hipLaunchKernelGGL((tsg_transpose_quads_kernel<T, false, 16, Q>), grid, dim3(256), 0, s, x, XQ, M, K, Mp, Kp, units, inv, rn, g);
             } else {
-                if (vec) hipLaunchKernelGGL((tsg_transpose_quads_kernel<T, true, 8, Q>), grid, dim3(256), 0, s, x, XQ, M, K, Mp, Kp, units, inv);
-                else hipLaunchKernelGGL((tsg_transpose_quads_kernel<T, false, 8, Q>), grid, dim3(256), 0, s, x, XQ, M, K, Mp, Kp, units, inv);
+                if (vec) hipLaunchKernelGGL((tsg_transpose_quads_kernel<T, true, 8, Q>), grid, dim3(256), 0, s, x, XQ, M, K, Mp, Kp, units, inv, rn, g);
+                else hipLaunchKernelGGL((tsg_transpose_quads_kernel<T, false, 8, Q>), grid, dim3(256), 0, s, x, XQ, M, K, Mp, Kp, units, inv, rn, g);
             }
             return hipGetLastError() == hipSuccess ? 0 : -1;
         });
@@ -581,9 +653,11 @@ int launch_transpose_quads(const void *X, int xtype, float *XQ, int M, int K, in
 
 // The row pass of an actquant call: inv and deq (float[M] each) of every row,
 // deq also to out when given, and with q8 the int8 q of the whole X (the
-// small-M walks).  An int8 X is refused (-1).
+// small-M walks).  With rn (float[M]) the row pass of a normquant call: the
+// RMSNorm of tsg_norm.h with gamma g (may be null) and eps comes first, and
+// rn[m] is stored too.  An int8 X is refused (-1).
 int launch_row_absmax(const void *X, int xtype, int M, int K, float *inv, float *deq, float *out, int8_t *q8,
-                      void *stream)
+                      void *stream, float *rn, const float *g, float eps)
 {
     if (M <= 0) return 0;
     if (xtype == kXI8) return -1;
@@ -595,13 +669,20 @@ int launch_row_absmax(const void *X, int xtype, int M, int K, float *inv, float 
         if constexpr (std::is_same_v<T, xi8>) {
             return -1;
         } else {
-            if (q8) {
-                if (vec) hipLaunchKernelGGL((tsg_row_absmax_kernel<T, true, true>), grid, dim3(256), 0, s, x, M, K, inv, deq, out, q8);
-                else hipLaunchKernelGGL((tsg_row_absmax_kernel<T, false, true>), grid, dim3(256), 0, s, x, M, K, inv, deq, out, q8);
-            } else {
-                if (vec) hipLaunchKernelGGL((tsg_row_absmax_kernel<T, true, false>), grid, dim3(256), 0, s, x, M, K, inv, deq, out, q8);
-                else hipLaunchKernelGGL((tsg_row_absmax_kernel<T, false, false>), grid, dim3(256), 0, s, x, M, K, inv, deq, out, q8);
-            }
+            auto go = [&](auto v, auto q, auto n) {
+                hipLaunchKernelGGL((tsg_row_absmax_kernel<T, decltype(v)::value, decltype(q)::value, decltype(n)::value>),
+                                   grid, dim3(256), 0, s, x, M, K, inv, deq, out, q8, rn, g, eps);
+            };
+            auto pick_q = [&](auto v, auto n) {
+                if (q8) go(v, std::true_type{}, n);
+                else go(v, std::false_type{}, n);
+            };
+            auto pick_v = [&](auto n) {
+                if (vec) pick_q(std::true_type{}, n);
+                else pick_q(std::false_type{}, n);
+            };
+            if (rn) pick_v(std::true_type{});
+            else pick_v(std::false_type{});
             return hipGetLastError() == hipSuccess ? 0 : -1;
         }
     });

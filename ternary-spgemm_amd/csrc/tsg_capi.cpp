@@ -84,8 +84,9 @@ struct tsg_tcsc {
     hipStream_t work_stream = nullptr;
     hipEvent_t work_ev = nullptr;
     bool work_used = false;
-    // scratch of the actquant calls (tsg_actquant.h): inv at d_aq[0, aq_rows),
-    // deq at d_aq[aq_rows, 2 aq_rows), and the int8 q (M x K) of a call that
+    // scratch of the actquant and normquant calls (tsg_actquant.h, tsg_norm.h):
+    // inv at d_aq[0, aq_rows), deq at d_aq[aq_rows, 2 aq_rows), the rn of a
+    // normquant call at d_aq[2 aq_rows, 3 aq_rows), and the int8 q (M x K) of a call that
     // runs a small-M walk.  Grow-only and shared by every stream like d_work:
     // the same event orders its reuse (work_begin / work_end)
     float *d_aq = nullptr;
@@ -189,7 +190,7 @@ int ensure_aq(tsg_tcsc *h, int rows, size_t q8, bool capturing)
         if (h->d_aq) HIP_TRY(hipFree(h->d_aq));
         h->d_aq = nullptr;
         h->aq_rows = 0;
-        if (hipMalloc(&h->d_aq, 2 * need * sizeof(float)) != hipSuccess)
+        if (hipMalloc(&h->d_aq, 3 * need * sizeof(float)) != hipSuccess)
             return fail(TSG_ERR_NOMEM, "hipMalloc of the activation-quantisation scales failed");
         h->aq_rows = need;
     }
@@ -449,6 +450,11 @@ struct Call {
     // caller's copy of it (may be null)
     bool quant = false;
     float *drs_out = nullptr;
+    // a normquant call (tsg_norm.h): an actquant call whose X goes through an
+    // RMSNorm with gamma dgamma (may be null) and eps first
+    bool norm = false;
+    const float *dgamma = nullptr;
+    float eps = 0.0f;
 };
 
 // Before a call stages its X^T: the work buffer holds it (ensure_work), and
@@ -481,11 +487,13 @@ int work_end(tsg_tcsc *h, const Call &c)
 }
 
 // The row pass of an actquant call, after work_begin: inv and deq of every row
-// into the scratch (and deq to the caller), for a walk also the int8 q
+// into the scratch (and deq to the caller), for a walk also the int8 q; of a
+// normquant call also rn, and everything is taken of the normalised row
 int quant_rows(tsg_tcsc *h, const Call &c, bool q8)
 {
     if (tsg::launch_row_absmax(c.dX, c.xtype, c.M, h->plan.K, h->d_aq, h->d_aq + h->aq_rows, c.drs_out,
-                               q8 ? h->d_aq8 : nullptr, c.s) != 0)
+                               q8 ? h->d_aq8 : nullptr, c.s, c.norm ? h->d_aq + 2 * h->aq_rows : nullptr, c.dgamma,
+                               c.eps) != 0)
         return fail(TSG_ERR_HIP, std::string("row pass launch: ") + hipGetErrorString(hipGetLastError()));
     return TSG_OK;
 }
@@ -536,10 +544,11 @@ int run_rx(tsg_tcsc *h, const CallPlan &p, const Call &c)
     if (rc) return rc;
     const float *inv = c.quant ? h->d_aq : nullptr;
     const float *drs = c.quant ? h->d_aq + h->aq_rows : c.drs;
+    const float *rn = c.norm ? h->d_aq + 2 * h->aq_rows : nullptr;
     if (K == 0) {
         // no X at all: chain is +0; X^T stays zero
         HIP_TRY(hipMemsetAsync(h->d_work, 0, (size_t)d.Mp * d.Kp * sizeof(float), c.s));
-    } else if (tsg::launch_transpose(c.dX, c.xtype, h->d_work, c.M, K, d.Mp, d.Kp, c.s, inv) != 0) {
+    } else if (tsg::launch_transpose(c.dX, c.xtype, h->d_work, c.M, K, d.Mp, d.Kp, c.s, inv, rn, c.dgamma) != 0) {
         return fail(TSG_ERR_HIP, std::string("transpose launch: ") + hipGetErrorString(hipGetLastError()));
     }
     int slot;
@@ -582,7 +591,7 @@ int run_jit(tsg_tcsc *h, const CallPlan &p, const tsg_tcsc::JitVariant &jv, cons
                             ? 4 * ((jv.nch - 1) * tsg::kJit64RowChunk - tsg::jit64_row_kbase(K, jv.nch, jv.nch - 1))
                             : 0;
     int rc;
-    const float *inv = nullptr, *drs = c.drs;
+    const float *inv = nullptr, *drs = c.drs, *rn = nullptr;
     if (!direct) {  // (direct: no staging kernel, the dispatcher's DMA reads X itself)
         rc = work_begin(h, p, c);
         if (!rc && c.quant) rc = quant_rows(h, c, false);
@@ -590,13 +599,15 @@ int run_jit(tsg_tcsc *h, const CallPlan &p, const tsg_tcsc::JitVariant &jv, cons
         if (c.quant) {
             inv = h->d_aq;
             drs = h->d_aq + h->aq_rows;
+            if (c.norm) rn = h->d_aq + 2 * h->aq_rows;
         }
         if (K == 0) {
             // no X at all: chain is +0; X^T stays zero
             HIP_TRY(hipMemsetAsync(h->d_work, 0, (size_t)d.Mp * d.Kp * sizeof(float), c.s));
         } else if ((r64 ? tsg::launch_transpose_quads(c.dX, c.xtype, h->d_work, c.M, K, d.Mp, d.Kp, jv.piece_rows, c.s,
-                                                      p.chunk, inv)
-                        : tsg::launch_transpose_pairs(c.dX, c.xtype, h->d_work, c.M, K, d.Mp, d.Kp, c.s, inv)) != 0) {
+                                                      p.chunk, inv, rn, c.dgamma)
+                        : tsg::launch_transpose_pairs(c.dX, c.xtype, h->d_work, c.M, K, d.Mp, d.Kp, c.s, inv, rn,
+                                                      c.dgamma)) != 0) {
             return fail(TSG_ERR_HIP, std::string("transpose launch: ") + hipGetErrorString(hipGetLastError()));
         }
     }
@@ -615,11 +626,14 @@ int run_jit(tsg_tcsc *h, const CallPlan &p, const tsg_tcsc::JitVariant &jv, cons
 
 int run_dev(tsg_tcsc *h, const void *dX, const float *db, const float *dalpha, void *dY, int64_t ldY, int M,
             int N, int K, hipStream_t s, bool prelu, int xtype = tsg::kXF32, int ytype = tsg::kYF32,
-            const float *drs = nullptr, const float *dcs = nullptr, bool quant = false, float *drs_out = nullptr)
+            const float *drs = nullptr, const float *dcs = nullptr, bool quant = false, float *drs_out = nullptr,
+            bool norm = false, const float *dgamma = nullptr, float eps = 0.0f)
 {
     if (!h) return fail(TSG_ERR_ARG, "null handle");
+    if (norm && !(std::isfinite(eps) && eps > 0.0f))  // refused before anything is enqueued
+        return fail(TSG_ERR_ARG, "eps=" + std::to_string(eps) + ": the normquant calls need a finite eps > 0");
     if (quant && xtype == tsg::kXI8)  // refused before anything is enqueued
-        return fail(TSG_ERR_ARG, "xtype=3 (int8): the actquant calls quantise an fp32, fp16 or bf16 X; an int8 X "
+        return fail(TSG_ERR_ARG, "xtype=3 (int8): the actquant and normquant calls quantise an fp32, fp16 or bf16 X; an int8 X "
                                  "goes to tcsc_hip_gemm_dev_scaled with its own scale");
     if (!tsg::xtype_ok(xtype))  // refused before anything is enqueued
         return fail(TSG_ERR_ARG,
@@ -643,7 +657,7 @@ int run_dev(tsg_tcsc *h, const void *dX, const float *db, const float *dalpha, v
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     HIP_TRY(hipStreamIsCapturing(s, &cap));
     const Call c{dX, xtype, db, dalpha, drs, dcs, dY, ytype, ldY, M, s, prelu, cap != hipStreamCaptureStatusNone,
-                 quant, drs_out};
+                 quant, drs_out, norm, dgamma, eps};
     CallPlan p = tsg::plan_call(h->plan, M);
     if (p.is_ell()) return run_ell(h, p, c);
     if (!p.is_jit()) return run_rx(h, p, c);
@@ -1444,6 +1458,27 @@ extern "C" int tcsc_hip_gemm_prelu_dev_actquant(tsg_tcsc *h, const void *dX, int
 {
     return run_dev(h, dX, db, dalpha, dY, ldY, M, N, K, (hipStream_t)stream, true, xtype, ytype, nullptr, dcol_scale,
                    true, drow_scale_out);
+}
+
+// Fused RMSNorm + activation quantisation (tsg_norm.h): the _actquant calls on
+// xn = (X * rn[m]) * gamma[k], made by the same two passes -- the row pass finds
+// rn first, the staging pass normalises what it loads before it quantises
+// (Call::norm, Call::dgamma, Call::eps)
+extern "C" int tcsc_hip_gemm_dev_normquant(tsg_tcsc *h, const void *dX, int xtype, const float *dgamma, float eps,
+                                           float *drow_scale_out, const float *dcol_scale, const float *db, void *dY,
+                                           int ytype, int64_t ldY, int M, int N, int K, void *stream)
+{
+    return run_dev(h, dX, db, nullptr, dY, ldY, M, N, K, (hipStream_t)stream, false, xtype, ytype, nullptr, dcol_scale,
+                   true, drow_scale_out, true, dgamma, eps);
+}
+
+extern "C" int tcsc_hip_gemm_prelu_dev_normquant(tsg_tcsc *h, const void *dX, int xtype, const float *dgamma, float eps,
+                                                 float *drow_scale_out, const float *dcol_scale, const float *db,
+                                                 const float *dalpha, void *dY, int ytype, int64_t ldY, int M, int N,
+                                                 int K, void *stream)
+{
+    return run_dev(h, dX, db, dalpha, dY, ldY, M, N, K, (hipStream_t)stream, true, xtype, ytype, nullptr, dcol_scale,
+                   true, drow_scale_out, true, dgamma, eps);
 }
 
 extern "C" int tcsc_hip_info(const tsg_tcsc *h, tsg_info *o)

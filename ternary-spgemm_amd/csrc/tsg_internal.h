@@ -338,22 +338,28 @@ int encode_fill(const int32_t *dW, int K, int N, const int32_t *d_csp, const int
 // K row-major of element type xtype (XType); the staged copies are fp32.
 // inv (float[M], default none): the staging pass quantises every value it
 // loads, xquant(v, inv[m]) (tsg_actquant.h; an actquant call, never an int8 X).
+// rn (float[M], with inv; default none) and g (float[K] or null): it normalises
+// first, xquant(xnorm(v, rn[m], g[k]), inv[m]) (tsg_norm.h; a normquant call).
 int launch_transpose(const void *X, int xtype, float *XT, int M, int K, int Mp, int Kp, void *stream,
-                     const float *inv = nullptr);
+                     const float *inv = nullptr, const float *rn = nullptr, const float *g = nullptr);
 // X [M][K] -> X^T in the k-pair layout of the jit kernel (Kp even, Mp even)
 int launch_transpose_pairs(const void *X, int xtype, float *XP, int M, int K, int Mp, int Kp, void *stream,
-                           const float *inv = nullptr);
+                           const float *inv = nullptr, const float *rn = nullptr, const float *g = nullptr);
 // X [M][K] -> the blocked k-quad layout of the 64-row image (Mp % 64 == 0, Kp % 192 == 0;
 // piece_rows 16 or 8, kJit64R16Flag), or with piece_rows 0 its row layout's
 // staged copy (kJit64RowFlag; Kp % 188 == 0)
 int launch_transpose_quads(const void *X, int xtype, float *XQ, int M, int K, int Mp, int Kp, int piece_rows,
-                           void *stream, int chunk = kJit64Chunk, const float *inv = nullptr);
+                           void *stream, int chunk = kJit64Chunk, const float *inv = nullptr,
+                           const float *rn = nullptr, const float *g = nullptr);
 // The row pass of an actquant call (tsg_row_absmax_kernel): inv[m] = 127 / a and
 // deq[m] = a / 127, a = max(max_k |X[m,k]|, 1e-5), for every row; deq also to
 // out (may be null); q8 (may be null): the int8 q of all of X, row-major [M][K],
-// for the small-M walks.  X is fp32, fp16 or bf16.
+// for the small-M walks.  X is fp32, fp16 or bf16.  rn (float[M], default none):
+// the row pass of a normquant call -- rn[m] = 1 / sqrtf(mean_k X[m,k]^2 + eps) in
+// the summation order of tsg_norm.h is stored too, and the maximum and q are
+// taken of (X[m,k] * rn[m]) * g[k] (g may be null).
 int launch_row_absmax(const void *X, int xtype, int M, int K, float *inv, float *deq, float *out, int8_t *q8,
-                      void *stream);
+                      void *stream, float *rn = nullptr, const float *g = nullptr, float eps = 0.0f);
 int launch_tcsc_rx(const float *XT, int Mp, const uint32_t *wstart, const uint32_t *ent,
                    const float *b, const float *alpha, const float *rs, const float *cs, void *Y, int ytype,
                    int64_t ldY, int M, int N, int Npad, int nch, int prelu, void *stream);

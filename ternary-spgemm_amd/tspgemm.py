@@ -53,6 +53,7 @@ EXPORTED_SYMBOLS = (
     "tcsc_hip_gemm_dev_xy", "tcsc_hip_gemm_prelu_dev_xy",
     "tcsc_hip_gemm_dev_scaled", "tcsc_hip_gemm_prelu_dev_scaled",
     "tcsc_hip_gemm_dev_actquant", "tcsc_hip_gemm_prelu_dev_actquant",
+    "tcsc_hip_gemm_dev_normquant", "tcsc_hip_gemm_prelu_dev_normquant",
 )
 
 # enum tsg_xtype (include/ternary_spgemm.h): element type of X on the _x calls
@@ -123,6 +124,10 @@ def lib() -> C.CDLL:
                                              C.c_int, vp]
     L.tcsc_hip_gemm_prelu_dev_actquant.argtypes = [H, vp, C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_int64, C.c_int,
                                                    C.c_int, C.c_int, vp]
+    L.tcsc_hip_gemm_dev_normquant.argtypes = [H, vp, C.c_int, vp, C.c_float, vp, vp, vp, vp, C.c_int, C.c_int64,
+                                              C.c_int, C.c_int, C.c_int, vp]
+    L.tcsc_hip_gemm_prelu_dev_normquant.argtypes = [H, vp, C.c_int, vp, C.c_float, vp, vp, vp, vp, vp, C.c_int,
+                                                    C.c_int64, C.c_int, C.c_int, C.c_int, vp]
     L.tcsc_hip_reserve.argtypes = [H, C.c_int]
     L.tcsc_hip_info.argtypes = [H, C.POINTER(tsg_info)]
     L.tcsc_hip_to_dense.argtypes = [H, vp, C.c_int, C.c_int]
@@ -464,6 +469,42 @@ def act_quant_ref(Xw) -> Tuple[np.ndarray, np.ndarray]:
     return q.astype(np.int8), deq
 
 
+def rms_norm_ref(Xw, gamma, eps) -> Tuple[np.ndarray, np.ndarray]:
+    """The RMSNorm of the normquant calls (include/ternary_spgemm.h
+    tcsc_hip_gemm_dev_normquant) in numpy, on the widened fp32 X [M, K]: every
+    operation fp32 and rounded once, the sum of squares in the contract's
+    shape -- 256 strided partial sums, each serial in ascending k, then a
+    balanced binary tree, neighbours first.  gamma: None or float32 [K].
+    Returns (xn float32 [M, K], rn float32 [M]); the call's Y is the actquant
+    call's on X = xn, so act_quant_ref(xn) gives its q and deq.  K = 0: no sum
+    and no division, xn is empty and rn is 0."""
+    Xw = np.asarray(Xw)
+    if Xw.dtype != np.float32 or Xw.ndim != 2:
+        raise TSGError(1, "rms_norm_ref", "Xw must be a float32 [M, K] array")
+    f = np.float32
+    M, K = Xw.shape
+    if gamma is not None:
+        gamma = np.asarray(gamma)
+        if gamma.dtype != np.float32 or gamma.shape != (K,):
+            raise TSGError(1, "rms_norm_ref", f"gamma must be None or a float32 [{K}] array")
+    if K == 0:
+        return Xw.copy(), np.zeros(M, f)
+    with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+        sq = (Xw * Xw).astype(f)
+        s = np.zeros((M, 256), f)  # +0
+        for k0 in range(0, K, 256):
+            w = min(256, K - k0)
+            s[:, :w] = (s[:, :w] + sq[:, k0:k0 + w]).astype(f)
+        for _ in range(8):
+            s = (s[:, 0::2] + s[:, 1::2]).astype(f)
+        ms = (s[:, 0] / f(K)).astype(f)
+        rn = (f(1.0) / np.sqrt((ms + f(eps)).astype(f)).astype(f)).astype(f)
+        xn = (Xw * rn[:, None]).astype(f)
+        if gamma is not None:
+            xn = (xn * gamma[None, :]).astype(f)
+    return xn, rn
+
+
 class registered_host:
     """Context manager: page-locks numpy arrays for repeated host-pointer
     calls (tcsc_hip_host_register), unlocks them on exit."""
@@ -758,8 +799,41 @@ class TCSCDevice:
         return self._torch_xy("gemm_torch_actquant", X, b, Y, alpha, out_dtype, narrow_y=True, col_scale=col_scale,
                               row_scale_out=row_scale_out, actquant=True)
 
+    def gemm_dev_normquant(self, dX: int, xtype: int, dgamma: Optional[int], eps: float, db: int, dY: int,
+                           ytype: int, M: int, stream: int = 0, dalpha: Optional[int] = None,
+                           ldY: Optional[int] = None, drow_scale_out: Optional[int] = None,
+                           dcol_scale: Optional[int] = None) -> None:
+        """gemm_dev_actquant with the RMSNorm in front of the quantisation made
+        inside the call too (tcsc_hip_gemm_dev_normquant): each row of dX
+        (fp32, fp16 or bf16) becomes (x * rn[m]) * gamma[k], rn = 1 / sqrt(
+        mean(x^2) + eps) (rms_norm_ref states the arithmetic), and that is
+        quantised and multiplied as on gemm_dev_actquant.  dgamma: None or a
+        device float[K]; eps: finite and > 0."""
+        ld = self.N if ldY is None else int(ldY)
+        if dalpha is None:
+            _check(lib().tcsc_hip_gemm_dev_normquant(self._h, dX, int(xtype), dgamma, float(eps), drow_scale_out,
+                                                     dcol_scale, db, dY, int(ytype), ld, M, self.N, self.K,
+                                                     stream or None), "tcsc_hip_gemm_dev_normquant")
+        else:
+            _check(lib().tcsc_hip_gemm_prelu_dev_normquant(self._h, dX, int(xtype), dgamma, float(eps),
+                                                           drow_scale_out, dcol_scale, db, dalpha, dY, int(ytype),
+                                                           ld, M, self.N, self.K, stream or None),
+                   "tcsc_hip_gemm_prelu_dev_normquant")
+
+    def gemm_torch_normquant(self, X, b, gamma, eps, Y=None, alpha=None, out_dtype=None, col_scale=None,
+                             row_scale_out=None):
+        """The input side of a BitNet-style BitLinear in one call: RMSNorm,
+        per-row int8 quantisation and the ternary product.  X as on
+        gemm_torch_actquant; gamma is None or a contiguous float32 [K] tensor
+        on the handle's device (a slice will do); eps is finite and > 0.  The
+        result is gemm_torch_actquant(xn, ...) bit for bit, xn =
+        rms_norm_ref(X.float(), gamma, eps)[0].  Everything else as on
+        gemm_torch_actquant.  Returns Y."""
+        return self._torch_xy("gemm_torch_normquant", X, b, Y, alpha, out_dtype, narrow_y=True, col_scale=col_scale,
+                              row_scale_out=row_scale_out, actquant=True, norm=True, gamma=gamma, eps=eps)
+
     def _torch_xy(self, where, X, b, Y, alpha, out_dtype, narrow_y, scaled=False, row_scale=None, col_scale=None,
-                  row_scale_out=None, actquant=False):
+                  row_scale_out=None, actquant=False, norm=False, gamma=None, eps=None):
         import torch
         dev = torch.device("cuda", self.device)
         ytypes = {torch.float32: TSG_Y_F32}
@@ -780,10 +854,11 @@ class TCSCDevice:
             raise TSGError(1, where, "X must be float32, float16 or bfloat16: an int8 X is quantised already "
                                      "(gemm_torch_scaled takes it with its row scale)")
         for name, t, shape in (("b", b, (self.N,)), ("alpha", alpha, (self.N,)), ("row_scale", row_scale, (M,)),
-                               ("col_scale", col_scale, (self.N,)), ("row_scale_out", row_scale_out, (M,))):
+                               ("col_scale", col_scale, (self.N,)), ("row_scale_out", row_scale_out, (M,)),
+                               ("gamma", gamma, (self.K,))):
             if t is None:
                 continue
-            if "_scale" in name and not isinstance(t, torch.Tensor):
+            if ("_scale" in name or name == "gamma") and not isinstance(t, torch.Tensor):
                 raise TSGError(1, where, f"{name} must be a tensor, got {type(t)}")
             if t.dtype != torch.float32 or t.device != dev or not t.is_contiguous() or tuple(t.shape) != shape:
                 raise TSGError(1, where, f"{name} must be a contiguous float32 {list(shape)} tensor on "
@@ -807,7 +882,12 @@ class TCSCDevice:
             raise TSGError(1, where, f"Y's rows overlap: stride(0) = {ldY} < N = {self.N}")
         stream = torch.cuda.current_stream(dev).cuda_stream
         dalpha = None if alpha is None else alpha.data_ptr()
-        if actquant:
+        if norm:
+            self.gemm_dev_normquant(X.data_ptr(), xtypes[X.dtype], None if gamma is None else gamma.data_ptr(), eps,
+                                    b.data_ptr(), Y.data_ptr(), ytypes[Y.dtype], M, stream, dalpha, ldY=ldY,
+                                    drow_scale_out=None if row_scale_out is None else row_scale_out.data_ptr(),
+                                    dcol_scale=None if col_scale is None else col_scale.data_ptr())
+        elif actquant:
             self.gemm_dev_actquant(X.data_ptr(), xtypes[X.dtype], b.data_ptr(), Y.data_ptr(), ytypes[Y.dtype], M,
                                    stream, dalpha, ldY=ldY,
                                    drow_scale_out=None if row_scale_out is None else row_scale_out.data_ptr(),
