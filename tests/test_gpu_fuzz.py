@@ -3,7 +3,8 @@ sparsity drawn over the regimes the automatic plan distinguishes (walk,
 producer/consumer walk, 64-row image with direct or staged X, 128-row image),
 K not a multiple of 4 included, each call compared on EVERY element with the
 BaseTCSC oracle (comp.h:25-69) on order-sensitive X, automatic and with each
-image pinned."""
+image pinned.  (The other entry points -- typed X and Y, a strided Y, the
+scales, actquant, normquant -- are fuzzed by test_gpu_call_fuzz.py.)"""
 import numpy as np
 import pytest
 

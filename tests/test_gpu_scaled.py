@@ -146,12 +146,17 @@ def _got_bits(t, ydtype):
     return _bits(t) if ydtype == "float32" else _ybits(t)
 
 
-def _outputs(M, N, ydtype):
-    """name -> (buffer, view, box, fill, only_view): a dense output and the odd view."""
+def _outputs(M, N, ydtype, c0=None, pad=0):
+    """name -> (buffer, view, box, fill, only_view): a dense output and the odd
+    view.  With a column offset c0: one output instead, "view" = rows 1..M,
+    columns c0..c0+N of an [M + 2, c0 + N + pad] buffer (test_gpu_call_fuzz)."""
     import torch
     dt = _tdtype(ydtype)
     f32 = ydtype == "float32"
     fill, only = (_fill, _assert_only_view_written) if f32 else (_fill16, _assert_only_view_written16)
+    if c0 is not None:
+        buf = torch.empty((M + 2, c0 + N + pad), dtype=dt, device="cuda")
+        return {"view": (buf, buf[1:M + 1, c0:c0 + N], (1, M + 1, c0, c0 + N), fill, only)}
     dense = torch.empty((M + 2, N), dtype=dt, device="cuda")
     odd = torch.empty((M + 2, N + 3), dtype=dt, device="cuda")
     return {"dense": (dense, dense[1:M + 1], (1, M + 1, 0, N), fill, only),
