@@ -405,6 +405,111 @@ int tcsc_hip_gemm_prelu_dev_normquant(tsg_tcsc *h, const void *dX, int xtype, co
                                       const float *dalpha, void *dY, int ytype, int64_t ldY, int M, int N, int K,
                                       void *stream);
 
+/* One descriptor call for all of the device calls above, with a fused epilogue
+ * after the projection: ReLU or ReLU^2, a gate multiply and a residual add on
+ * the finished fp32 value, before the one rounding to the Y type.  A gated FFN
+ * computes down(act(gate(x)) * up(x)) and every attention output and FFN down
+ * projection is followed by h = h + proj(x); with these three steps in the
+ * kernel that stores Y the caller runs no elementwise pass over an [M, N]
+ * tensor.  The descriptor maps one to one onto what a device call carries
+ * internally, so later features extend this struct and not the list of entry
+ * points; the calls above stay as they are.
+ *
+ * in_mode picks the call the descriptor restates: TSG_IN_PLAIN is _scaled (and
+ * with both scales NULL _xy), TSG_IN_ACTQUANT is _actquant, TSG_IN_NORMQUANT is
+ * _normquant; act = TSG_ACT_PRELU picks its PReLU twin.
+ *
+ * Contract.  All arithmetic is fp32, one rounding per operation, no fused
+ * multiply-add and no contraction anywhere:
+ *
+ *   t = what the call of the chosen in_mode adds b to, scaled as on _scaled /
+ *       _actquant / _normquant (a blocked handle: after its last block)
+ *   y = t + db[n]                                       rounded
+ *   a = act(y):  TSG_ACT_NONE   y
+ *                TSG_ACT_PRELU  y > 0 ? y : dalpha[n] * y           (as ever)
+ *                TSG_ACT_RELU   y > 0 ? y : (y != y ? y : +0.0f)    -0 -> +0, a NaN
+ *                                                                   stays a NaN
+ *                TSG_ACT_RELU2  r = RELU(y);  r * r     rounded once; may overflow
+ *                                                       to +inf
+ *   if (dmul) a = a * widen(mul[m * ldmul + n])         rounded
+ *   if (dadd) a = a + widen(add[m * ldadd + n])         rounded, never contracted
+ *                                                       with the multiply before it
+ *   Y[m * ldY + n] = a rounded ONCE to ytype, as on _xy
+ *
+ * Widening an fp16 or bf16 operand element to fp32 is exact.  A NULL operand
+ * means its operation is not performed (not a multiply by 1, nothing added).
+ * The operands may hold any IEEE value -- 0, -0, subnormal, inf, NaN -- and Y is
+ * the IEEE result of the operations above (a NaN's payload is not promised).
+ * Operands.  dmul and dadd are [M, N] device arrays of multype / addtype
+ * (tsg_ytype values: fp32, fp16, bf16), each with its own row stride ldmul /
+ * ldadd in elements of its own type, >= N.  They need only the alignment of
+ * their element (slices are fine) and are never written (but see in place).
+ * Isolation: no value outside [m * ld, m * ld + N) of rows 0 .. M-1 reaches Y.
+ * Load rule, the mirror of _xy's store rule: a lane's full-width row segment
+ * (its 8 to 128 columns inside N) that starts 16-byte aligned is loaded with
+ * 16-byte loads, anything else -- the ragged last column tile, an odd ld, a
+ * misaligned base -- element by element; the result is the same bit for bit.
+ * In place.  dadd may be exactly dY, with addtype == ytype and ldadd == ldY:
+ * h += proj(x).  The same holds for dmul.  Every element is then read by the
+ * lane that stores it, before the store.  Any other overlap between Y and an
+ * operand is the caller's error: the result is unspecified, nothing faults.
+ * Legacy equivalence.  With act TSG_ACT_NONE or TSG_ACT_PRELU and both
+ * operands NULL the call IS the existing call of its in_mode: the same path,
+ * the same kernel arguments and flags, the same bits; nothing new is launched.
+ * Errors.  TSG_ERR_ARG with a message that names the field, nothing enqueued:
+ * a NULL d; struct_size != sizeof(tsg_gemm_ex); reserved != 0; an in_mode, act,
+ * xtype, ytype, multype or addtype outside its enum; ldY, or the ld of a passed
+ * operand, smaller than N; TSG_ACT_PRELU without dalpha; TSG_X_I8 in a
+ * quantising in_mode; in TSG_IN_NORMQUANT an eps that is not finite and > 0; a
+ * field of another in_mode that is not NULL (dgamma outside NORMQUANT,
+ * drow_scale in a quantising in_mode, drow_scale_out in PLAIN).  dalpha is read
+ * for TSG_ACT_PRELU only and otherwise ignored.  tsg_gemm_ex_check performs
+ * exactly these checks on the host -- no device, no handle -- and
+ * tcsc_hip_gemm_dev_ex calls it right after its null-handle check.
+ * As on the call of the same in_mode: stream semantics, tcsc_hip_reserve and
+ * graph capture, the kernel and image an M picks, the direct-X rule, the work
+ * buffer and the scratch, the written-range guarantee of Y.  The epilogue adds
+ * no allocation, no launch and no synchronisation: the operands are two more
+ * pointers of the kernel that stores Y.
+ * Out of scope: SiLU, GELU and SwiGLU (a bit-exact exp needs a contract of its
+ * own); quantising Y; operands broadcast per row or per column; the
+ * host-pointer calls; the plugin header (tcsc_hip_plugin.hpp); ShardedTCSC.
+ * Extension: no reference counterpart.
+ *
+ * Layout (LP64, no padding, 144 bytes): byte offset of every field on the
+ * right.  A later version may only append fields and grow struct_size. */
+enum tsg_act { TSG_ACT_NONE = 0, TSG_ACT_PRELU = 1, TSG_ACT_RELU = 2, TSG_ACT_RELU2 = 3 };
+enum tsg_in_mode { TSG_IN_PLAIN = 0, TSG_IN_ACTQUANT = 1, TSG_IN_NORMQUANT = 2 };
+
+typedef struct tsg_gemm_ex {
+    uint32_t struct_size;       /*   0  sizeof(tsg_gemm_ex); anything else: TSG_ERR_ARG naming struct_size */
+    int32_t in_mode;            /*   4  tsg_in_mode */
+    const void *dX;             /*   8  M x K row-major elements of xtype */
+    int32_t xtype;              /*  16  tsg_xtype */
+    int32_t act;                /*  20  tsg_act */
+    const float *dgamma;        /*  24  NORMQUANT only (as on _normquant, may be NULL there); else NULL */
+    float eps;                  /*  32  NORMQUANT only; ignored otherwise */
+    int32_t ytype;              /*  36  tsg_ytype */
+    const float *drow_scale;    /*  40  PLAIN only (as on _scaled); NULL in the quantising modes */
+    float *drow_scale_out;      /*  48  quantising modes only (as on _actquant); NULL in PLAIN */
+    const float *dcol_scale;    /*  56  float[N] or NULL */
+    const float *db;            /*  64  float[N] */
+    const float *dalpha;        /*  72  float[N]; read for TSG_ACT_PRELU only (then required) */
+    const void *dmul;           /*  80  gate operand, [M, N] of multype; NULL: no multiply */
+    int64_t ldmul;              /*  88  elements of multype per row of dmul, >= N */
+    const void *dadd;           /*  96  residual operand, [M, N] of addtype; NULL: no add */
+    int64_t ldadd;              /* 104  elements of addtype per row of dadd, >= N */
+    int32_t multype;            /* 112  tsg_ytype values */
+    int32_t addtype;            /* 116  tsg_ytype values */
+    void *dY;                   /* 120  M x N elements of ytype */
+    int64_t ldY;                /* 128  elements of ytype per row of dY, >= N */
+    uint64_t reserved;          /* 136  must be 0 */
+} tsg_gemm_ex;
+
+int tcsc_hip_gemm_dev_ex(tsg_tcsc *h, const tsg_gemm_ex *d, int M, int N, int K, void *stream);
+/* host only: no device, no handle */
+int tsg_gemm_ex_check(const tsg_gemm_ex *d, int M, int N, int K);
+
 /* Pre-allocates the per-handle work buffer for row counts up to max_M and, on
  * the weight-compiled kernel, compiles every code image a call with M <= max_M
  * rows runs (and the small-M images), so no later such call allocates or

@@ -29,6 +29,7 @@
 #include <type_traits>
 
 #include "tsg_actquant.h"
+#include "tsg_epilogue.h"
 #include "tsg_internal.h"
 #include "tsg_norm.h"
 #include "tsg_scale.h"
@@ -430,7 +431,7 @@ __global__ __launch_bounds__(kRxWaves * 64, 8 / kRxWaves) void tsg_tcsc_rx_kerne
     const float *__restrict__ XT, int Mp, const uint32_t *__restrict__ wstart,
     const uint32_t *__restrict__ ent, const float *__restrict__ b, const float *__restrict__ alpha,
     float *__restrict__ Y, int64_t ldY, int ytype, int M, int N, int nch, int mtiles, int ntiles,
-    const float *__restrict__ rs, const float *__restrict__ cs)
+    const float *__restrict__ rs, const float *__restrict__ cs, Epi ep)
 {
     __shared__ __attribute__((aligned(16))) char lds[kRxLdsBytes];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -472,9 +473,10 @@ __global__ __launch_bounds__(kRxWaves * 64, 8 / kRxWaves) void tsg_tcsc_rx_kerne
         __syncthreads();
     }
     if (ncol0 >= N) return;
-    if ((rs != nullptr) | (cs != nullptr)) {
+    if (((rs != nullptr) | (cs != nullptr)) && !(ytype & kYEpi)) {
         // a scaled call (uniform; tsg_scale.h): ((chain * rs[m]) * cs[n]) + b[n],
         // three roundings, then the PReLU and the store of any Y type
+        // (one with a fused epilogue too goes to that branch, below)
 #pragma unroll
         for (int r = 0; r < 4; r++) {
             const int m = m0 + 4 * lane + r;
@@ -497,6 +499,33 @@ __global__ __launch_bounds__(kRxWaves * 64, 8 / kRxWaves) void tsg_tcsc_rx_kerne
         return;
     }
     if (ytype != kYF32) {
+        if (ytype & kYEpi) {
+            // a call with a fused epilogue (uniform: the launcher's flag;
+            // tsg_epilogue.h): the scaled value (a missing scale's multiply not
+            // performed), the PReLU, then per group of 8 columns the lane's
+            // own gate and residual elements, ReLU / ReLU^2, * gate, +
+            // residual, and the store of any Y type
+            const int yt = ytype & kYTypeMask;
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const int m = m0 + 4 * lane + r;
+                if (m >= M) continue;
+                int nc0 = ncol0;
+                const float *bs = b, *alphas = alpha, *rss = rs, *css = cs;
+                asm volatile("" : "+s"(nc0), "+s"(bs), "+s"(alphas), "+s"(rss), "+s"(css));
+                const bool has_rs = rss != nullptr, has_cs = css != nullptr;
+                const float rm = has_rs ? rss[m] : 0.0f;
+                ystore_seg_epi<kRxNW>(Y, yt, ldY, ep, m, nc0, N - nc0, [&](int c) {
+                    const int n = nc0 + c < N ? nc0 + c : N - 1;
+                    const float acc = c < 8 ? a0[4 * (c & 7) + r] : c < 16 ? a1[4 * (c & 7) + r]
+                                     : c < 24 ? a2[4 * (c & 7) + r] : a3[4 * (c & 7) + r];
+                    float y = scale_bias(acc, has_rs, rm, has_cs, has_cs ? css[n] : 0.0f, bs[n]);
+                    if (PRELU) y = (y > 0) ? y : alphas[n] * y;  // comp_prelu.h:57-67
+                    return y;
+                });
+            }
+            return;
+        }
         // a 16-bit Y (uniform): the same fp32 value, rounded once and stored
         // 8 columns at a time (tsg_ytype.h); ldY counts 16-bit elements
 #pragma unroll
@@ -689,18 +718,19 @@ int launch_row_absmax(const void *X, int xtype, int M, int K, float *inv, float 
 }
 
 int launch_tcsc_rx(const float *XT, int Mp, const uint32_t *wstart, const uint32_t *ent,
-                   const float *b, const float *alpha, const float *rs, const float *cs, void *Y, int ytype,
-                   int64_t ldY, int M, int N, int Npad, int nch, int prelu, void *stream)
+                   const float *b, const float *alpha, const float *rs, const float *cs, const Epi &ep, void *Y,
+                   int ytype, int64_t ldY, int M, int N, int Npad, int nch, int prelu, void *stream)
 {
     hipStream_t s = (hipStream_t)stream;
+    if (ep.on()) ytype |= kYEpi;  // the kernel's one test for a call with a fused epilogue (tsg_epilogue.h)
     const int mtiles = Mp / kRxTileM, ntiles = Npad / kRxTileCols;
     const dim3 grid((unsigned)(mtiles * ntiles)), block(kRxWaves * kLanes);
     if (prelu)
         hipLaunchKernelGGL((tsg_tcsc_rx_kernel<true>), grid, block, 0, s, XT, Mp, wstart, ent, b, alpha,
-                           static_cast<float *>(Y), ldY, ytype, M, N, nch, mtiles, ntiles, rs, cs);
+                           static_cast<float *>(Y), ldY, ytype, M, N, nch, mtiles, ntiles, rs, cs, ep);
     else
         hipLaunchKernelGGL((tsg_tcsc_rx_kernel<false>), grid, block, 0, s, XT, Mp, wstart, ent, b, alpha,
-                           static_cast<float *>(Y), ldY, ytype, M, N, nch, mtiles, ntiles, rs, cs);
+                           static_cast<float *>(Y), ldY, ytype, M, N, nch, mtiles, ntiles, rs, cs, ep);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

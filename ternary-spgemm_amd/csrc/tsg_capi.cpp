@@ -455,6 +455,9 @@ struct Call {
     bool norm = false;
     const float *dgamma = nullptr;
     float eps = 0.0f;
+    // the fused epilogue of a tcsc_hip_gemm_dev_ex call (tsg_epilogue.h); none
+    // on every other call
+    tsg::Epi ep;
 };
 
 // Before a call stages its X^T: the work buffer holds it (ensure_work), and
@@ -524,9 +527,9 @@ int run_ell(tsg_tcsc *h, const CallPlan &p, const Call &c0)
     const tsg_tcsc::EllVariant &e = h->ell[p.ell];
     const int N = h->plan.N, K = h->plan.K;
     const int lrc = p.kernel == Kernel::kEllPc
-                        ? tsg::launch_tcsc_ell_pc(p.ell, c.dX, c.xtype, e.d_ent, e.d_tab, c.db, c.dalpha, c.drs, c.dcs, c.dY, c.ytype,
+                        ? tsg::launch_tcsc_ell_pc(p.ell, c.dX, c.xtype, e.d_ent, e.d_tab, c.db, c.dalpha, c.drs, c.dcs, c.ep, c.dY, c.ytype,
                                                   c.ldY,                                                  c.M, N, K, e.img.C, e.img.nch, c.prelu ? 1 : 0, c.s)
-                        : tsg::launch_tcsc_ell(p.ell, c.dX, c.xtype, e.d_ent, e.d_tab, c.db, c.dalpha, c.drs, c.dcs, c.dY, c.ytype, c.ldY,
+                        : tsg::launch_tcsc_ell(p.ell, c.dX, c.xtype, e.d_ent, e.d_tab, c.db, c.dalpha, c.drs, c.dcs, c.ep, c.dY, c.ytype, c.ldY,
                                                c.M,                                               N, K, e.img.C, e.img.nch, e.img.xb, e.img.zr, c.prelu ? 1 : 0, c.s);
     if (lrc != 0)
         return fail(TSG_ERR_HIP, std::string("small-M kernel launch: ") + hipGetErrorString(hipGetLastError()));
@@ -554,7 +557,7 @@ int run_rx(tsg_tcsc *h, const CallPlan &p, const Call &c)
     int slot;
     rc = timing_begin(h, c.capturing, c.s, slot);
     if (rc) return rc;
-    if (tsg::launch_tcsc_rx(h->d_work, d.Mp, h->d_seg, h->d_ent, c.db, c.dalpha, drs, c.dcs, c.dY, c.ytype, c.ldY, c.M, N,
+    if (tsg::launch_tcsc_rx(h->d_work, d.Mp, h->d_seg, h->d_ent, c.db, c.dalpha, drs, c.dcs, c.ep, c.dY, c.ytype, c.ldY, c.M, N,
                             h->rimg.Npad, h->rimg.nch, c.prelu ? 1 : 0, c.s) != 0)
         return fail(TSG_ERR_HIP, std::string("tcsc launch: ") + hipGetErrorString(hipGetLastError()));
     rc = timing_end(h, slot, c.s);
@@ -615,7 +618,7 @@ int run_jit(tsg_tcsc *h, const CallPlan &p, const tsg_tcsc::JitVariant &jv, cons
     rc = timing_begin(h, c.capturing, c.s, slot);
     if (rc) return rc;
     if (tsg::launch_tcsc_jit(jv.mod, direct ? static_cast<const float *>(c.dX) : h->d_work, d.Mp, jv.d_wcode, c.db,
-                             c.dalpha, drs, c.dcs, c.dY, c.ytype, c.ldY, c.M, N,
+                             c.dalpha, drs, c.dcs, c.ep, c.dY, c.ytype, c.ldY, c.M, N,
                              jv.Npad, jv.nch, c.prelu ? 1 : 0, h->d_status, jv.nw * jv.waves, waves, p.gn, p.gm, p.tmask,
                              c.s, p.tile_m, direct ? K : 0, lastadj, p.xtouch, p.tnear) != 0)
         return fail(TSG_ERR_HIP, std::string("tcsc launch: ") + hipGetErrorString(hipGetLastError()));
@@ -627,7 +630,7 @@ int run_jit(tsg_tcsc *h, const CallPlan &p, const tsg_tcsc::JitVariant &jv, cons
 int run_dev(tsg_tcsc *h, const void *dX, const float *db, const float *dalpha, void *dY, int64_t ldY, int M,
             int N, int K, hipStream_t s, bool prelu, int xtype = tsg::kXF32, int ytype = tsg::kYF32,
             const float *drs = nullptr, const float *dcs = nullptr, bool quant = false, float *drs_out = nullptr,
-            bool norm = false, const float *dgamma = nullptr, float eps = 0.0f)
+            bool norm = false, const float *dgamma = nullptr, float eps = 0.0f, const tsg::Epi &ep = tsg::Epi())
 {
     if (!h) return fail(TSG_ERR_ARG, "null handle");
     if (norm && !(std::isfinite(eps) && eps > 0.0f))  // refused before anything is enqueued
@@ -657,7 +660,7 @@ int run_dev(tsg_tcsc *h, const void *dX, const float *db, const float *dalpha, v
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     HIP_TRY(hipStreamIsCapturing(s, &cap));
     const Call c{dX, xtype, db, dalpha, drs, dcs, dY, ytype, ldY, M, s, prelu, cap != hipStreamCaptureStatusNone,
-                 quant, drs_out, norm, dgamma, eps};
+                 quant, drs_out, norm, dgamma, eps, ep};
     CallPlan p = tsg::plan_call(h->plan, M);
     if (p.is_ell()) return run_ell(h, p, c);
     if (!p.is_jit()) return run_rx(h, p, c);
@@ -1479,6 +1482,82 @@ extern "C" int tcsc_hip_gemm_prelu_dev_normquant(tsg_tcsc *h, const void *dX, in
 {
     return run_dev(h, dX, db, dalpha, dY, ldY, M, N, K, (hipStream_t)stream, true, xtype, ytype, nullptr, dcol_scale,
                    true, drow_scale_out, true, dgamma, eps);
+}
+
+// The descriptor call (include/ternary_spgemm.h tsg_gemm_ex): every device call
+// above as one struct that maps onto Call, plus the fused epilogue
+// (tsg_epilogue.h).  The checks are host arithmetic on the descriptor alone, so
+// that they can be tested without a device.
+static_assert(sizeof(tsg_gemm_ex) == 144 && offsetof(tsg_gemm_ex, reserved) == 136, "the layout the header spells out");
+static_assert(TSG_ACT_RELU == tsg::kEpiRelu && TSG_ACT_RELU2 == tsg::kEpiRelu2, "act values in Epi::bits");
+extern "C" int tsg_gemm_ex_check(const tsg_gemm_ex *d, int M, int N, int K)
+{
+    (void)M;
+    (void)K;
+    if (!d) return fail(TSG_ERR_ARG, "d: null descriptor");
+    if (d->struct_size != sizeof(tsg_gemm_ex))
+        return fail(TSG_ERR_ARG, "struct_size=" + std::to_string(d->struct_size) + " is not sizeof(tsg_gemm_ex) = " +
+                                     std::to_string(sizeof(tsg_gemm_ex)));
+    if (d->reserved != 0) return fail(TSG_ERR_ARG, "reserved must be 0");
+    if (d->in_mode < TSG_IN_PLAIN || d->in_mode > TSG_IN_NORMQUANT)
+        return fail(TSG_ERR_ARG, "in_mode=" + std::to_string(d->in_mode) +
+                                     " is not a tsg_in_mode (0 plain, 1 actquant, 2 normquant)");
+    if (d->act < TSG_ACT_NONE || d->act > TSG_ACT_RELU2)
+        return fail(TSG_ERR_ARG, "act=" + std::to_string(d->act) + " is not a tsg_act (0 none, 1 prelu, 2 relu, 3 relu2)");
+    if (!tsg::xtype_ok(d->xtype))
+        return fail(TSG_ERR_ARG,
+                    "xtype=" + std::to_string(d->xtype) + " is not a tsg_xtype (0 fp32, 1 fp16, 2 bf16, 3 int8)");
+    if (!tsg::ytype_ok(d->ytype))
+        return fail(TSG_ERR_ARG, "ytype=" + std::to_string(d->ytype) + " is not a tsg_ytype (0 fp32, 1 fp16, 2 bf16)");
+    if (!tsg::ytype_ok(d->multype))
+        return fail(TSG_ERR_ARG, "multype=" + std::to_string(d->multype) + " is not a tsg_ytype (0 fp32, 1 fp16, 2 bf16)");
+    if (!tsg::ytype_ok(d->addtype))
+        return fail(TSG_ERR_ARG, "addtype=" + std::to_string(d->addtype) + " is not a tsg_ytype (0 fp32, 1 fp16, 2 bf16)");
+    if (d->ldY < N) return fail(TSG_ERR_ARG, "ldY=" + std::to_string(d->ldY) + " is less than N=" + std::to_string(N));
+    if (d->dmul && d->ldmul < N)
+        return fail(TSG_ERR_ARG, "ldmul=" + std::to_string(d->ldmul) + " is less than N=" + std::to_string(N));
+    if (d->dadd && d->ldadd < N)
+        return fail(TSG_ERR_ARG, "ldadd=" + std::to_string(d->ldadd) + " is less than N=" + std::to_string(N));
+    if (d->act == TSG_ACT_PRELU && !d->dalpha) return fail(TSG_ERR_ARG, "dalpha is NULL and act is TSG_ACT_PRELU");
+    const bool quant = d->in_mode != TSG_IN_PLAIN, norm = d->in_mode == TSG_IN_NORMQUANT;
+    if (quant && d->xtype == TSG_X_I8)
+        return fail(TSG_ERR_ARG, "xtype=3 (int8): the quantising in_modes take an fp32, fp16 or bf16 X; an int8 X goes "
+                                 "to TSG_IN_PLAIN with its own drow_scale");
+    if (norm && !(std::isfinite(d->eps) && d->eps > 0.0f))
+        return fail(TSG_ERR_ARG, "eps=" + std::to_string(d->eps) + ": TSG_IN_NORMQUANT needs a finite eps > 0");
+    if (!norm && d->dgamma) return fail(TSG_ERR_ARG, "dgamma belongs to TSG_IN_NORMQUANT and must be NULL in this in_mode");
+    if (quant && d->drow_scale)
+        return fail(TSG_ERR_ARG, "drow_scale belongs to TSG_IN_PLAIN and must be NULL in the quantising in_modes");
+    if (!quant && d->drow_scale_out)
+        return fail(TSG_ERR_ARG, "drow_scale_out belongs to the quantising in_modes and must be NULL in TSG_IN_PLAIN");
+    return TSG_OK;
+}
+
+extern "C" int tcsc_hip_gemm_dev_ex(tsg_tcsc *h, const tsg_gemm_ex *d, int M, int N, int K, void *stream)
+{
+    if (!h) return fail(TSG_ERR_ARG, "null handle");
+    const int rc = tsg_gemm_ex_check(d, M, N, K);
+    if (rc) return rc;
+    // the epilogue as the kernels take it; an operand that is exactly Y (the
+    // in-place form) is marked, so that the kernel loads it through Y itself
+    tsg::Epi ep;
+    if (d->act >= TSG_ACT_RELU) ep.bits |= d->act;  // kEpiRelu, kEpiRelu2
+    if (d->dmul) {
+        ep.mul = d->dmul;
+        ep.ldmul = d->ldmul;
+        ep.bits |= d->multype << tsg::kEpiMulShift;
+        if (d->dmul == d->dY && d->multype == d->ytype && d->ldmul == d->ldY) ep.bits |= tsg::kEpiMulIsY;
+    }
+    if (d->dadd) {
+        ep.add = d->dadd;
+        ep.ldadd = d->ldadd;
+        ep.bits |= d->addtype << tsg::kEpiAddShift;
+        if (d->dadd == d->dY && d->addtype == d->ytype && d->ldadd == d->ldY) ep.bits |= tsg::kEpiAddIsY;
+    }
+    const bool prelu = d->act == TSG_ACT_PRELU, quant = d->in_mode != TSG_IN_PLAIN;
+    return run_dev(h, d->dX, d->db, prelu ? d->dalpha : nullptr, d->dY, d->ldY, M, N, K, (hipStream_t)stream, prelu,
+                   d->xtype, d->ytype, d->drow_scale, d->dcol_scale, quant, d->drow_scale_out,
+                   d->in_mode == TSG_IN_NORMQUANT, d->dgamma, d->eps, ep);
 }
 
 extern "C" int tcsc_hip_info(const tsg_tcsc *h, tsg_info *o)

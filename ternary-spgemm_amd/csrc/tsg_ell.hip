@@ -41,6 +41,7 @@
 #include <cstdlib>
 #include <type_traits>
 
+#include "tsg_epilogue.h"
 #include "tsg_internal.h"
 #include "tsg_scale.h"
 #include "tsg_xtype.h"
@@ -247,7 +248,7 @@ template <typename T, int LG, int RPL, int WPG, int LA, bool PRELU, bool SCALED>
 __device__ __forceinline__ void ell_kernel_body(
     const T *__restrict__ X, const uint4 *__restrict__ ent, const uint2 *__restrict__ tab,
     const float *__restrict__ b, const float *__restrict__ alpha, const float *__restrict__ rs,
-    const float *__restrict__ cs, float *__restrict__ Y, int64_t ldY, int ytype, int M,
+    const float *__restrict__ cs, const Epi &ep, float *__restrict__ Y, int64_t ldY, int ytype, int M,
     int N, int K, int C, int nch, int steps, int nsg, int xb, int zr)
 {
     constexpr int MT = LG * RPL;                     // M rows of the tile
@@ -320,7 +321,9 @@ __device__ __forceinline__ void ell_kernel_body(
             if (m >= M) break;
             float v = scale_bias(y[r], has_rs, has_rs ? rs[m] : 0.0f, has_cs, cn, bn);
             if (PRELU) v = (v > 0) ? v : an * v;     // comp_prelu.h:57-67
-            if (ytype != kYF32)
+            if (ytype & kYEpi)  // a fused epilogue (uniform: the launcher's flag; tsg_epilogue.h)
+                epi_store1(Y, ytype & kYTypeMask, ldY, ep, m, n, v);
+            else if (ytype != kYF32)
                 ystore1(Y, ytype, (size_t)m * (size_t)ldY + n, v);
             else
                 Y[(size_t)m * (size_t)ldY + n] = v;
@@ -346,19 +349,20 @@ __global__ __launch_bounds__(WPG * 64) void tsg_tcsc_ell_kernel(
     const float *__restrict__ b, const float *__restrict__ alpha, float *__restrict__ Y, int64_t ldY, int ytype, int M,
     int N, int K, int C, int nch, int steps, int nsg, int xb, int zr)
 {
-    ell_kernel_body<T, LG, RPL, WPG, LA, PRELU, false>(X, ent, tab, b, alpha, nullptr, nullptr, Y, ldY, ytype, M, N, K, C,
-                                                       nch, steps, nsg, xb, zr);
+    ell_kernel_body<T, LG, RPL, WPG, LA, PRELU, false>(X, ent, tab, b, alpha, nullptr, nullptr, Epi{}, Y, ldY, ytype, M, N,
+                                                       K, C, nch, steps, nsg, xb, zr);
 }
 
-// ... and with an epilogue scale (launch_ell_la picks it when the call passes one)
+// ... and with an epilogue scale or a fused epilogue (tsg_epilogue.h; ep, with
+// the kYEpi flag in ytype): launch_ell_la picks it when the call passes either
 template <typename T, int LG, int RPL, int WPG, int LA, bool PRELU>
 __global__ __launch_bounds__(WPG * 64) void tsg_tcsc_ell_scaled_kernel(
     const T *__restrict__ X, const uint4 *__restrict__ ent, const uint2 *__restrict__ tab,
     const float *__restrict__ b, const float *__restrict__ alpha, const float *__restrict__ rs,
-    const float *__restrict__ cs, float *__restrict__ Y, int64_t ldY, int ytype, int M,
+    const float *__restrict__ cs, Epi ep, float *__restrict__ Y, int64_t ldY, int ytype, int M,
     int N, int K, int C, int nch, int steps, int nsg, int xb, int zr)
 {
-    ell_kernel_body<T, LG, RPL, WPG, LA, PRELU, true>(X, ent, tab, b, alpha, rs, cs, Y, ldY, ytype, M, N, K, C, nch,
+    ell_kernel_body<T, LG, RPL, WPG, LA, PRELU, true>(X, ent, tab, b, alpha, rs, cs, ep, Y, ldY, ytype, M, N, K, C, nch,
                                                       steps, nsg, xb, zr);
 }
 
@@ -405,7 +409,7 @@ template <typename T, int MT, int E, bool PRELU>
 __global__ __launch_bounds__(64 * (MT + E / 8)) void tsg_tcsc_ell_pc_kernel(
     const T *__restrict__ X, const uint4 *__restrict__ ent, const uint2 *__restrict__ tab,
     const float *__restrict__ b, const float *__restrict__ alpha, const float *__restrict__ rs,
-    const float *__restrict__ cs, float *__restrict__ Y, int64_t ldY, int ytype, int M,
+    const float *__restrict__ cs, Epi ep, float *__restrict__ Y, int64_t ldY, int ytype, int M,
     int N, int K, int C, int nsg)
 {
     using S = PcShape<MT, E>;
@@ -485,11 +489,13 @@ __global__ __launch_bounds__(64 * (MT + E / 8)) void tsg_tcsc_ell_pc_kernel(
             lds_barrier();
         }
         if (n >= N || m0 + r >= M) return;
-        if (ytype & kYScaled) {  // a scaled call (uniform: the launcher's flag; tsg_scale.h)
-            const int yt = ytype & ~kYScaled;
+        if (ytype & (kYScaled | kYEpi)) {  // a scaled call, or one with a fused epilogue (uniform: the launcher's flags; tsg_scale.h, tsg_epilogue.h)
+            const int yt = ytype & kYTypeMask;
             float v = scale_bias(y, rs != nullptr, rs ? rs[m0 + r] : 0.0f, cs != nullptr, cs ? cs[n] : 0.0f, b[n]);
             if (PRELU) v = (v > 0) ? v : alpha[n] * v;   // comp_prelu.h:57-67
-            if (yt != kYF32)
+            if (ytype & kYEpi)
+                epi_store1(Y, yt, ldY, ep, m0 + r, n, v);
+            else if (yt != kYF32)
                 ystore1(Y, yt, (size_t)(m0 + r) * (size_t)ldY + n, v);
             else
                 Y[(size_t)(m0 + r) * (size_t)ldY + n] = v;
@@ -596,7 +602,7 @@ __global__ __launch_bounds__(64 * (MT + E / 8)) void tsg_tcsc_ell_pc_kernel(
 namespace {
 
 template <typename T, int LG, int RPL, int WPG, int LA>
-int launch_ell_la(const T *X, const uint4 *ent, const uint2 *tab, const float *b, const float *alpha, const float *rs, const float *cs, float *Y,
+int launch_ell_la(const T *X, const uint4 *ent, const uint2 *tab, const float *b, const float *alpha, const float *rs, const float *cs, const Epi &ep, float *Y,
                   int64_t ldY, int ytype, int M, int N, int K, int C, int nch, int xb, int zr, int prelu, hipStream_t s)
 {
     constexpr int MT = LG * RPL, CPW = 64 / LG;
@@ -605,13 +611,14 @@ int launch_ell_la(const T *X, const uint4 *ent, const uint2 *tab, const float *b
     const int steps = nch == 1 ? 1 : 2 * nch;
     const size_t lds = ell_lds_floats(C, MT, xb, zr) * sizeof(float);
     const dim3 grid((unsigned)(nsg * mtiles)), block(WPG * 64);
-    if (rs || cs) {  // a scaled call: the kernel with the scaled epilogue
+    if (rs || cs || ep.on()) {  // a scaled call, or one with a fused epilogue: the kernel with that epilogue
+        if (ep.on()) ytype |= kYEpi;  // its one test for a fused epilogue (tsg_internal.h)
         if (prelu)
             hipLaunchKernelGGL((tsg_tcsc_ell_scaled_kernel<T, LG, RPL, WPG, LA, true>), grid, block, lds, s, X, ent, tab,
-                               b, alpha, rs, cs, Y, ldY, ytype, M, N, K, C, nch, steps, nsg, xb, zr);
+                               b, alpha, rs, cs, ep, Y, ldY, ytype, M, N, K, C, nch, steps, nsg, xb, zr);
         else
             hipLaunchKernelGGL((tsg_tcsc_ell_scaled_kernel<T, LG, RPL, WPG, LA, false>), grid, block, lds, s, X, ent, tab,
-                               b, alpha, rs, cs, Y, ldY, ytype, M, N, K, C, nch, steps, nsg, xb, zr);
+                               b, alpha, rs, cs, ep, Y, ldY, ytype, M, N, K, C, nch, steps, nsg, xb, zr);
     } else if (prelu)
         hipLaunchKernelGGL((tsg_tcsc_ell_kernel<T, LG, RPL, WPG, LA, true>), grid, block, lds, s, X, ent, tab, b, alpha,
                            Y, ldY, ytype, M, N, K, C, nch, steps, nsg, xb, zr);
@@ -633,12 +640,12 @@ int pick_la()
 }
 
 template <typename T, int LG, int RPL, int WPG>
-int launch_ell_t(const T *X, const uint4 *ent, const uint2 *tab, const float *b, const float *alpha, const float *rs, const float *cs, float *Y,
+int launch_ell_t(const T *X, const uint4 *ent, const uint2 *tab, const float *b, const float *alpha, const float *rs, const float *cs, const Epi &ep, float *Y,
                  int64_t ldY, int ytype, int M, int N, int K, int C, int nch, int xb, int zr, int prelu, hipStream_t s)
 {
     if (pick_la() == 2)
-        return launch_ell_la<T, LG, RPL, WPG, 2>(X, ent, tab, b, alpha, rs, cs, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
-    return launch_ell_la<T, LG, RPL, WPG, 1>(X, ent, tab, b, alpha, rs, cs, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
+        return launch_ell_la<T, LG, RPL, WPG, 2>(X, ent, tab, b, alpha, rs, cs, ep, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
+    return launch_ell_la<T, LG, RPL, WPG, 1>(X, ent, tab, b, alpha, rs, cs, ep, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
 }
 
 }  // namespace
@@ -659,7 +666,7 @@ namespace {
 constexpr int64_t kEllWideWgs = 224;  // 7/8 of the CUs
 
 template <typename T, int LG, int RPL>
-int launch_lg(const T *X, const uint4 *e, const uint2 *t, const float *b, const float *alpha, const float *rs, const float *cs, float *Y,
+int launch_lg(const T *X, const uint4 *e, const uint2 *t, const float *b, const float *alpha, const float *rs, const float *cs, const Epi &ep, float *Y,
               int64_t ldY, int ytype, int M, int N, int K, int C, int nch, int xb, int zr, int prelu, hipStream_t s)
 {
     constexpr int MT = LG * RPL, CPW = 64 / LG;
@@ -669,11 +676,11 @@ int launch_lg(const T *X, const uint4 *e, const uint2 *t, const float *b, const 
         const char *v = knob_value("TSG_ELL_WPG");
         return v ? atoi(v) : 0;
     }();
-    if (env_wpg == 4) return launch_ell_t<T, LG, RPL, 4>(X, e, t, b, alpha, rs, cs, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
+    if (env_wpg == 4) return launch_ell_t<T, LG, RPL, 4>(X, e, t, b, alpha, rs, cs, ep, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
     if constexpr (RPL <= 2) {
-        if (env_wpg == 8) return launch_ell_t<T, LG, RPL, 8>(X, e, t, b, alpha, rs, cs, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
+        if (env_wpg == 8) return launch_ell_t<T, LG, RPL, 8>(X, e, t, b, alpha, rs, cs, ep, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
         if (env_wpg == 16)
-            return launch_ell_t<T, LG, RPL, 16>(X, e, t, b, alpha, rs, cs, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
+            return launch_ell_t<T, LG, RPL, 16>(X, e, t, b, alpha, rs, cs, ep, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
     }
     if constexpr (RPL <= 2) {
         auto one_round = [&](int64_t wpg) {  // >= 7/8 of the CUs busy, no second round
@@ -681,14 +688,14 @@ int launch_lg(const T *X, const uint4 *e, const uint2 *t, const float *b, const 
             return wgs >= kEllWideWgs && wgs <= 256 * per_cu;
         };
         if (one_round(16))
-            return launch_ell_t<T, LG, RPL, 16>(X, e, t, b, alpha, rs, cs, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
-        if (one_round(8)) return launch_ell_t<T, LG, RPL, 8>(X, e, t, b, alpha, rs, cs, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
+            return launch_ell_t<T, LG, RPL, 16>(X, e, t, b, alpha, rs, cs, ep, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
+        if (one_round(8)) return launch_ell_t<T, LG, RPL, 8>(X, e, t, b, alpha, rs, cs, ep, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
         if (waves > 256 * per_cu * 8)
-            return launch_ell_t<T, LG, RPL, 16>(X, e, t, b, alpha, rs, cs, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
+            return launch_ell_t<T, LG, RPL, 16>(X, e, t, b, alpha, rs, cs, ep, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
         if (waves > 256 * per_cu * 4)
-            return launch_ell_t<T, LG, RPL, 8>(X, e, t, b, alpha, rs, cs, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
+            return launch_ell_t<T, LG, RPL, 8>(X, e, t, b, alpha, rs, cs, ep, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
     }
-    return launch_ell_t<T, LG, RPL, 4>(X, e, t, b, alpha, rs, cs, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
+    return launch_ell_t<T, LG, RPL, 4>(X, e, t, b, alpha, rs, cs, ep, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
 }
 
 // lanes per column of an M tile: the default, or TSG_ELL_LG (diagnostic sweeps)
@@ -708,7 +715,7 @@ constexpr size_t pc_lds(int C)
 }
 
 template <typename T, int MT, int E>
-int launch_pc_t(const T *X, const uint4 *ent, const uint2 *tab, const float *b, const float *alpha, const float *rs, const float *cs, float *Y,
+int launch_pc_t(const T *X, const uint4 *ent, const uint2 *tab, const float *b, const float *alpha, const float *rs, const float *cs, const Epi &ep, float *Y,
                 int64_t ldY, int ytype, int M, int N, int K, int C, int prelu, hipStream_t s)
 {
     using S = PcShape<MT, E>;
@@ -717,10 +724,10 @@ int launch_pc_t(const T *X, const uint4 *ent, const uint2 *tab, const float *b, 
     const size_t lds = pc_lds<MT, E>(C);
     const dim3 grid((unsigned)(nsg * mtiles)), block(S::NT);
     if (prelu)
-        hipLaunchKernelGGL((tsg_tcsc_ell_pc_kernel<T, MT, E, true>), grid, block, lds, s, X, ent, tab, b, alpha, rs, cs, Y, ldY, ytype, M,
+        hipLaunchKernelGGL((tsg_tcsc_ell_pc_kernel<T, MT, E, true>), grid, block, lds, s, X, ent, tab, b, alpha, rs, cs, ep, Y, ldY, ytype, M,
                            N, K, C, nsg);
     else
-        hipLaunchKernelGGL((tsg_tcsc_ell_pc_kernel<T, MT, E, false>), grid, block, lds, s, X, ent, tab, b, alpha, rs, cs, Y, ldY, ytype,
+        hipLaunchKernelGGL((tsg_tcsc_ell_pc_kernel<T, MT, E, false>), grid, block, lds, s, X, ent, tab, b, alpha, rs, cs, ep, Y, ldY, ytype,
                            M, N, K, C, nsg);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
@@ -764,11 +771,12 @@ size_t ell_pc_lds_bytes(int variant, int C)
 }
 
 int launch_tcsc_ell_pc(int variant, const void *X, int xtype, const uint32_t *ent, const uint32_t *tab, const float *b,
-                       const float *alpha, const float *rs, const float *cs, void *Yv, int ytype, int64_t ldY, int M, int N, int K, int C, int nch,
+                       const float *alpha, const float *rs, const float *cs, const Epi &ep, void *Yv, int ytype, int64_t ldY, int M, int N, int K, int C, int nch,
                        int prelu, void *stream)
 {
     float *Y = static_cast<float *>(Yv);  // elements of ytype; the kernels' epilogue casts (tsg_ytype.h)
     if (rs || cs) ytype |= kYScaled;      // the kernel's one test for a scaled call (tsg_internal.h)
+    if (ep.on()) ytype |= kYEpi;          // ... and for one with a fused epilogue
     // one stream per column, X chunk + ring within a workgroup's LDS
     if (nch != 1 || ell_pc_lds_bytes(variant, C) == 0 || ell_pc_lds_bytes(variant, C) > kLdsBytes) return -2;
     hipStream_t s = (hipStream_t)stream;
@@ -778,9 +786,9 @@ int launch_tcsc_ell_pc(int variant, const void *X, int xtype, const uint32_t *en
     return with_xtype(X, xtype, [&](auto *x) {
         using T = std::remove_cv_t<std::remove_pointer_t<decltype(x)>>;
         switch (phase) {
-        case 16: return launch_pc_t<T, 1, 16>(x, e, t, b, alpha, rs, cs, Y, ldY, ytype, M, N, K, C, prelu, s);
-        case 64: return launch_pc_t<T, 1, 64>(x, e, t, b, alpha, rs, cs, Y, ldY, ytype, M, N, K, C, prelu, s);
-        default: return launch_pc_t<T, 1, 32>(x, e, t, b, alpha, rs, cs, Y, ldY, ytype, M, N, K, C, prelu, s);  // 1 consumer, 4 producers
+        case 16: return launch_pc_t<T, 1, 16>(x, e, t, b, alpha, rs, cs, ep, Y, ldY, ytype, M, N, K, C, prelu, s);
+        case 64: return launch_pc_t<T, 1, 64>(x, e, t, b, alpha, rs, cs, ep, Y, ldY, ytype, M, N, K, C, prelu, s);
+        default: return launch_pc_t<T, 1, 32>(x, e, t, b, alpha, rs, cs, ep, Y, ldY, ytype, M, N, K, C, prelu, s);  // 1 consumer, 4 producers
         }
     });
 }
@@ -789,13 +797,13 @@ namespace {
 
 template <typename T>
 int launch_ell_variant(int variant, const T *X, const uint4 *e, const uint2 *t, const float *b, const float *alpha, const float *rs, const float *cs,
-                       float *Y, int64_t ldY, int ytype, int M, int N, int K, int C, int nch, int xb, int zr, int prelu,
+                       const Epi &ep, float *Y, int64_t ldY, int ytype, int M, int N, int K, int C, int nch, int xb, int zr, int prelu,
                        hipStream_t s)
 {
 #define TSG_ELL_LG(lg, rpl) \
-    case lg: return launch_lg<T, lg, rpl>(X, e, t, b, alpha, rs, cs, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s)
+    case lg: return launch_lg<T, lg, rpl>(X, e, t, b, alpha, rs, cs, ep, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s)
     switch (variant) {
-    case 0: return launch_ell_t<T, 1, 1, 1>(X, e, t, b, alpha, rs, cs, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);  // MT = 1
+    case 0: return launch_ell_t<T, 1, 1, 1>(X, e, t, b, alpha, rs, cs, ep, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);  // MT = 1
     case 1:                                                                                   // MT = 4
         switch (pick_lg(4)) {
             TSG_ELL_LG(4, 1);
@@ -828,7 +836,7 @@ int launch_ell_variant(int variant, const T *X, const uint4 *e, const uint2 *t, 
 }  // namespace
 
 int launch_tcsc_ell(int variant, const void *X, int xtype, const uint32_t *ent, const uint32_t *tab, const float *b,
-                    const float *alpha, const float *rs, const float *cs, void *Yv, int ytype, int64_t ldY, int M, int N, int K, int C, int nch, int xb,
+                    const float *alpha, const float *rs, const float *cs, const Epi &ep, void *Yv, int ytype, int64_t ldY, int M, int N, int K, int C, int nch, int xb,
                     int zr, int prelu, void *stream)
 {
     float *Y = static_cast<float *>(Yv);  // elements of ytype; the kernels' epilogue casts (tsg_ytype.h)
@@ -839,7 +847,7 @@ int launch_tcsc_ell(int variant, const void *X, int xtype, const uint32_t *ent, 
     const uint4 *e = reinterpret_cast<const uint4 *>(ent);
     const uint2 *t = reinterpret_cast<const uint2 *>(tab);
     return with_xtype(X, xtype, [&](auto *x) {
-        return launch_ell_variant(variant, x, e, t, b, alpha, rs, cs, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
+        return launch_ell_variant(variant, x, e, t, b, alpha, rs, cs, ep, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
     });
 }
 

@@ -36,8 +36,36 @@ enum YType { kYF32 = 0, kYF16 = 1, kYBF16 = 2 };
 // test `ytype != kYF32`.  (The ELL walk has a kernel of its own for scaled
 // calls, tsg_tcsc_ell_scaled_kernel; rx tests the two pointers.)
 constexpr int kYScaled = 0x100;
+// A second flag next to it, set by the launchers of every kernel that stores Y
+// when the call has a fused epilogue (tsg_epilogue.h: ReLU / ReLU^2, a gate
+// multiply, a residual add; tcsc_hip_gemm_dev_ex).  Such a call takes a branch
+// of its own inside the kernels' `ytype != kYF32` test, which serves the
+// scales and every Y type too; a call without one never sets it and runs the
+// code it ran before.
+constexpr int kYEpi = 0x200;
+constexpr int kYTypeMask = 0xff;
 inline bool ytype_ok(int ytype) { return ytype >= kYF32 && ytype <= kYBF16; }
 inline size_t ytype_size(int ytype) { return ytype == kYF32 ? 4 : 2; }
+
+// The fused epilogue of one call, as the launchers hand it to the kernels (by
+// value, after cs).  mul / add: the gate and the residual operand, [M, N] of
+// their own element type (YType values) with ldmul / ldadd elements from one
+// row to the next; null: the operation is not performed.  bits: the activation
+// (kEpiRelu, kEpiRelu2; 0: none -- the PReLU stays the kernels' prelu flag),
+// the two operand types, and an alias bit per operand that is exactly Y (same
+// pointer, type and ld: the in-place form), which the kernel then loads
+// through its own Y pointer (Y is __restrict__ there).
+constexpr int kEpiRelu = 2, kEpiRelu2 = 3, kEpiActMask = 3;  // tsg_act values
+constexpr int kEpiMulShift = 2, kEpiAddShift = 4;             // two bits of YType each
+constexpr int kEpiMulIsY = 0x40, kEpiAddIsY = 0x80;
+struct Epi {
+    const void *mul = nullptr;
+    int64_t ldmul = 0;
+    const void *add = nullptr;
+    int64_t ldadd = 0;
+    int bits = 0;
+    bool on() const { return (bits & kEpiActMask) != 0 || mul != nullptr || add != nullptr; }
+};
 
 // ---------------------------------------------------------------------------
 // "rx" (register-X) kernel (tsg_tcsc_rx_kernel)
@@ -251,9 +279,10 @@ struct JitModule {
 // xtouch: the per-group code touches (v[lane128 + 1]) spread over the lines;
 // tnear: the code touches' window starts at the step's own position;
 // rs, cs: the epilogue scales of the _scaled calls (float[M], float[N]; either
-// may be null: tsg_scale.h), taken by every kernel below that stores Y
+// may be null: tsg_scale.h), taken by every kernel below that stores Y;
+// ep: the call's fused epilogue (Epi above; tsg_epilogue.h), likewise
 int launch_tcsc_jit(const JitModule &jm, const float *XT, int Mp, const uint32_t *wcode,
-                    const float *b, const float *alpha, const float *rs, const float *cs, void *Y, int ytype,
+                    const float *b, const float *alpha, const float *rs, const float *cs, const Epi &ep, void *Y, int ytype,
                     int64_t ldY, int M, int N, int Npad, int nch, int prelu, uint32_t *status, int tile_cols,
                     int waves, int gn, int gm, int tmask, void *stream, int tile_m = kJitTileM, int xrow = 0, int lastadj = 0, int xtouch = 0,
                     int tnear = 0);
@@ -301,7 +330,7 @@ constexpr int kEllSchedZeroRows = 8;
 void build_ell_image(const int32_t *csp, const int32_t *csn, const int32_t *rip, const int32_t *rin, int K, int N,
                      int Cmax, int MT, EllImage &img, int copies = 1, bool sched = false);
 int launch_tcsc_ell(int variant, const void *X, int xtype, const uint32_t *ent, const uint32_t *tab, const float *b,
-                    const float *alpha, const float *rs, const float *cs, void *Y, int ytype, int64_t ldY, int M, int N, int K, int C, int nch, int xb,
+                    const float *alpha, const float *rs, const float *cs, const Epi &ep, void *Y, int ytype, int64_t ldY, int M, int N, int K, int C, int nch, int xb,
                     int zr, int prelu, void *stream);
 // the producer/consumer walk (tsg_tcsc_ell_pc_kernel) of variant 0 (M = 1) when
 // K fits one chunk and the chunk plus its LDS ring fit kLdsBytes
@@ -309,7 +338,7 @@ int launch_tcsc_ell(int variant, const void *X, int xtype, const uint32_t *ent, 
 constexpr size_t kLdsBytes = 160 * 1024;
 size_t ell_pc_lds_bytes(int variant, int C);
 int launch_tcsc_ell_pc(int variant, const void *X, int xtype, const uint32_t *ent, const uint32_t *tab, const float *b,
-                       const float *alpha, const float *rs, const float *cs, void *Y, int ytype, int64_t ldY, int M, int N, int K, int C, int nch,
+                       const float *alpha, const float *rs, const float *cs, const Epi &ep, void *Y, int ytype, int64_t ldY, int M, int N, int K, int C, int nch,
                        int prelu, void *stream);
 
 // Environment knobs (csrc/tsg_knobs.cpp): A/B studies and tests, none of
@@ -361,7 +390,7 @@ int launch_transpose_quads(const void *X, int xtype, float *XQ, int M, int K, in
 int launch_row_absmax(const void *X, int xtype, int M, int K, float *inv, float *deq, float *out, int8_t *q8,
                       void *stream, float *rn = nullptr, const float *g = nullptr, float eps = 0.0f);
 int launch_tcsc_rx(const float *XT, int Mp, const uint32_t *wstart, const uint32_t *ent,
-                   const float *b, const float *alpha, const float *rs, const float *cs, void *Y, int ytype,
+                   const float *b, const float *alpha, const float *rs, const float *cs, const Epi &ep, void *Y, int ytype,
                    int64_t ldY, int M, int N, int Npad, int nch, int prelu, void *stream);
 
 }  // namespace tsg

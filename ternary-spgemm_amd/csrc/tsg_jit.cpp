@@ -936,6 +936,8 @@ constexpr const char *kJitArgsMarker = "tsg_jit_args_ldy";
 constexpr const char *kJitYtypeMarker = "tsg_jit_args_ytype";
 // ... and with the two epilogue scales rs, cs after ytype
 constexpr const char *kJitScaleMarker = "tsg_jit_args_scale";
+// ... and with the fused epilogue (Epi, by value) after them
+constexpr const char *kJitEpiMarker = "tsg_jit_args_epi";
 
 // The dispatcher of a stream width: tsg_jit.co (kJitNW columns per wave) or
 // tsg_jit_w<nw>.co (same kernel built with TSG_JIT_NW=nw, Makefile); 4-wave
@@ -1090,6 +1092,13 @@ std::string JitModule::load(const std::vector<uint32_t> &code, int nw, int waves
         return std::string("jit template ") + template_name(nw, waves, r64, half, pair) +
                " predates the dispatcher's scale arguments (no " + kJitScaleMarker + "); rebuild it";
     }
+    // and for the fused epilogue after the scales
+    if (hipModuleGetFunction(&mark, m, kJitEpiMarker) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipModuleUnload(m);
+        return std::string("jit template ") + template_name(nw, waves, r64, half, pair) +
+               " predates the dispatcher's epilogue argument (no " + kJitEpiMarker + "); rebuild it";
+    }
     module = m;
     function = fn;
     probe = pf;
@@ -1113,16 +1122,18 @@ int launch_jit_probe(const JitModule &jm, uint32_t *status, void *stream)
 }
 
 int launch_tcsc_jit(const JitModule &jm, const float *XT, int Mp, const uint32_t *wcode, const float *b,
-                    const float *alpha, const float *rs, const float *cs, void *Y, int ytype, int64_t ldY, int M,
-                    int N, int Npad, int nch, int prelu, uint32_t *status, int tile_cols, int waves, int gn, int gm,
+                    const float *alpha, const float *rs, const float *cs, const Epi &ep, void *Y, int ytype,
+                    int64_t ldY, int M, int N, int Npad, int nch, int prelu, uint32_t *status, int tile_cols, int waves, int gn, int gm,
                     int tmask, void *stream, int tile_m, int xrow, int lastadj, int xtouch, int tnear)
 {
     int mtiles = Mp / tile_m, ntiles = Npad / tile_cols;
     if (rs || cs) ytype |= kYScaled;  // the dispatcher's one test ahead of its fp32 path (tsg_jit_kernel.hip)
+    if (ep.on()) ytype |= kYEpi;      // likewise: a call with a fused epilogue (tsg_epilogue.h)
     void *params[] = {(void *)&XT, (void *)&Mp, (void *)&wcode, (void *)&b, (void *)&alpha, (void *)&Y,
                       (void *)&M, (void *)&N, (void *)&nch, (void *)&mtiles, (void *)&ntiles, (void *)&prelu,
                       (void *)&status, (void *)&gn, (void *)&gm, (void *)&tmask, (void *)&xrow, (void *)&lastadj,
-                      (void *)&xtouch, (void *)&tnear, (void *)&ldY, (void *)&ytype, (void *)&rs, (void *)&cs};
+                      (void *)&xtouch, (void *)&tnear, (void *)&ldY, (void *)&ytype, (void *)&rs, (void *)&cs,
+                      (void *)&ep};
     hipError_t e = hipModuleLaunchKernel((hipFunction_t)jm.function, (unsigned)(mtiles * ntiles), 1, 1,
                                          (unsigned)waves * 64u, 1, 1, 0, (hipStream_t)stream, params, nullptr);
     return e == hipSuccess ? 0 : -1;

@@ -45,6 +45,7 @@
 
 #include <cstdint>
 
+#include "tsg_epilogue.h"
 #include "tsg_jit_map.h"
 #include "tsg_scale.h"
 #include "tsg_ytype.h"
@@ -181,6 +182,10 @@ extern "C" __global__ __launch_bounds__(64) void tsg_jit_args_ytype() {}
 // ... and for the two after that, the epilogue scales rs and cs, with the
 // kYScaled flag in ytype when one of them is passed (looked up last)
 extern "C" __global__ __launch_bounds__(64) void tsg_jit_args_scale() {}
+// ... and for the fused epilogue after them (tsg_epilogue.h: the gate and the
+// residual operand with their row strides, and the bits), with the kYEpi flag
+// in ytype when the call has one (looked up last)
+extern "C" __global__ __launch_bounds__(64) void tsg_jit_args_epi() {}
 
 // (the half ring: two workgroups per CU, so at most 256 VGPRs -- two waves per SIMD)
 extern "C" __global__ __launch_bounds__(kJThreads, kJHalf ? 2 : 1) void TSG_JIT_KERNEL_NAME(
@@ -188,7 +193,7 @@ extern "C" __global__ __launch_bounds__(kJThreads, kJHalf ? 2 : 1) void TSG_JIT_
     const float *__restrict__ b, const float *__restrict__ alpha, float *__restrict__ Y, int M, int N,
     int nch, int mtiles, int ntiles, int prelu, uint32_t *__restrict__ status, int gn, int gm,
     int tmask, int xrow, int lastadj, int xtouch, int tnear, int64_t ldY, int ytype,
-    const float *__restrict__ rs, const float *__restrict__ cs)
+    const float *__restrict__ rs, const float *__restrict__ cs, tsg::Epi ep)
 {
     __shared__ __attribute__((aligned(16))) char lds[kJRing * kJBufBytes];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -399,6 +404,34 @@ extern "C" __global__ __launch_bounds__(kJThreads, kJHalf ? 2 : 1) void TSG_JIT_
     if (ncol0 >= N) return;
     if (kJPair && (lane >> 5) != rhalf) return;  // the pair's other wave holds these rows
     if (__builtin_expect(ytype != tsg::kYF32, 0)) {  // (out of line: the fp32 path keeps its layout)
+        if (ytype & tsg::kYEpi) {
+            // a call with a fused epilogue (uniform; tsg_epilogue.h): the
+            // scaled branch below -- a missing scale's multiply not performed,
+            // so an unscaled call is served too -- then, per group of 8
+            // columns, the lane's own gate and residual elements, ReLU /
+            // ReLU^2, * gate, + residual, and the store of any Y type.  Behind
+            // a flag of ytype for the reason given below; an operand that is
+            // Y itself is loaded through Y (tsg_epilogue.h epi_base).
+            const int yt = ytype & tsg::kYTypeMask;
+#pragma unroll
+            for (int r = 0; r < kJRowsPerLane; r++) {
+                const int m = m0 + kJRowsPerLane * lane + r;
+                if (m >= M) continue;
+                // this branch's own copies, fenced like the ones below
+                int nc0 = ncol0;
+                const float *bs = b, *alphas = alpha, *rss = rs, *css = cs;
+                asm volatile("" : "+s"(nc0), "+s"(bs), "+s"(alphas), "+s"(rss), "+s"(css));
+                const bool has_rs = rss != nullptr, has_cs = css != nullptr;
+                const float rm = has_rs ? rss[m] : 0.0f;
+                tsg::ystore_seg_epi<kJNW>(Y, yt, ldY, ep, m, nc0, N - nc0, [&](int c) {
+                    const int n = nc0 + c < N ? nc0 + c : N - 1;
+                    float y = tsg::scale_bias(acc_of(c, r), has_rs, rm, has_cs, has_cs ? css[n] : 0.0f, bs[n]);
+                    if (prelu) y = (y > 0) ? y : alphas[n] * y;   // comp_prelu.h:57-67
+                    return y;
+                });
+            }
+            return;
+        }
         if (ytype & tsg::kYScaled) {
             // a scaled call (uniform; tsg_scale.h): ((chain * rs[m]) * cs[n]) +
             // b[n], three roundings, then the PReLU and the store of any Y type

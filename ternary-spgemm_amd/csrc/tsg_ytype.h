@@ -102,6 +102,9 @@ __device__ __forceinline__ void ystore_seg(void *Y, int ytype, size_t first, int
 // float4 stores, anything else as 4-byte stores of the valid elements -- the
 // rule of the kernels' own fp32 stores.  Again val(c) is held once per column
 // and the (uniform) type is looked at per group of 8.
+// (tsg_epilogue.h ystore_seg_epi is this body again with the operand loads in
+// the loop, and the kernels' epilogue branches repeat the scaled branch's
+// lambda: a change to the store rule here is made there too.)
 template <int NW, typename F>
 __device__ __forceinline__ void ystore_seg_any(void *Y, int ytype, size_t first, int nvalid, F &&val)
 {

@@ -54,12 +54,17 @@ EXPORTED_SYMBOLS = (
     "tcsc_hip_gemm_dev_scaled", "tcsc_hip_gemm_prelu_dev_scaled",
     "tcsc_hip_gemm_dev_actquant", "tcsc_hip_gemm_prelu_dev_actquant",
     "tcsc_hip_gemm_dev_normquant", "tcsc_hip_gemm_prelu_dev_normquant",
+    "tcsc_hip_gemm_dev_ex", "tsg_gemm_ex_check",
 )
 
 # enum tsg_xtype (include/ternary_spgemm.h): element type of X on the _x calls
 TSG_X_F32, TSG_X_F16, TSG_X_BF16, TSG_X_I8 = 0, 1, 2, 3
 # enum tsg_ytype: element type of Y on the _xy calls
 TSG_Y_F32, TSG_Y_F16, TSG_Y_BF16 = 0, 1, 2
+# enum tsg_act, enum tsg_in_mode: the descriptor call (tcsc_hip_gemm_dev_ex)
+TSG_ACT_NONE, TSG_ACT_PRELU, TSG_ACT_RELU, TSG_ACT_RELU2 = 0, 1, 2, 3
+TSG_IN_PLAIN, TSG_IN_ACTQUANT, TSG_IN_NORMQUANT = 0, 1, 2
+_ACTS = {"none": TSG_ACT_NONE, "prelu": TSG_ACT_PRELU, "relu": TSG_ACT_RELU, "relu2": TSG_ACT_RELU2}
 
 
 class TSGError(RuntimeError):
@@ -74,6 +79,23 @@ class tsg_info(C.Structure):
                 ("tcsc_bytes", C.c_int64), ("image_bytes", C.c_int64), ("work_bytes", C.c_int64),
                 ("chunk_rows", C.c_int32), ("tile_rows", C.c_int32), ("tile_cols", C.c_int32),
                 ("reserved", C.c_int32)]
+
+
+class tsg_gemm_ex(C.Structure):
+    """The descriptor of tcsc_hip_gemm_dev_ex (include/ternary_spgemm.h spells
+    out the layout: 144 bytes, no padding).  A fresh one has struct_size set
+    and everything else zero / NULL."""
+    _fields_ = [("struct_size", C.c_uint32), ("in_mode", C.c_int32), ("dX", C.c_void_p), ("xtype", C.c_int32),
+                ("act", C.c_int32), ("dgamma", C.c_void_p), ("eps", C.c_float), ("ytype", C.c_int32),
+                ("drow_scale", C.c_void_p), ("drow_scale_out", C.c_void_p), ("dcol_scale", C.c_void_p),
+                ("db", C.c_void_p), ("dalpha", C.c_void_p), ("dmul", C.c_void_p), ("ldmul", C.c_int64),
+                ("dadd", C.c_void_p), ("ldadd", C.c_int64), ("multype", C.c_int32), ("addtype", C.c_int32),
+                ("dY", C.c_void_p), ("ldY", C.c_int64), ("reserved", C.c_uint64)]
+
+    def __init__(self, **kw):
+        super().__init__(**kw)
+        if "struct_size" not in kw:
+            self.struct_size = C.sizeof(tsg_gemm_ex)
 
 
 _LIB: Optional[C.CDLL] = None
@@ -128,6 +150,8 @@ def lib() -> C.CDLL:
                                               C.c_int, C.c_int, C.c_int, vp]
     L.tcsc_hip_gemm_prelu_dev_normquant.argtypes = [H, vp, C.c_int, vp, C.c_float, vp, vp, vp, vp, vp, C.c_int,
                                                     C.c_int64, C.c_int, C.c_int, C.c_int, vp]
+    L.tcsc_hip_gemm_dev_ex.argtypes = [H, C.POINTER(tsg_gemm_ex), C.c_int, C.c_int, C.c_int, vp]
+    L.tsg_gemm_ex_check.argtypes = [C.POINTER(tsg_gemm_ex), C.c_int, C.c_int, C.c_int]
     L.tcsc_hip_reserve.argtypes = [H, C.c_int]
     L.tcsc_hip_info.argtypes = [H, C.POINTER(tsg_info)]
     L.tcsc_hip_to_dense.argtypes = [H, vp, C.c_int, C.c_int]
@@ -505,6 +529,49 @@ def rms_norm_ref(Xw, gamma, eps) -> Tuple[np.ndarray, np.ndarray]:
     return xn, rn
 
 
+def epilogue_ref(y32, act, alpha=None, mul=None, add=None) -> np.ndarray:
+    """The fused epilogue of the descriptor call (include/ternary_spgemm.h
+    tcsc_hip_gemm_dev_ex) in numpy fp32, one rounding per line.  y32: float32
+    [M, N], the value after + b[n] (what the fp32 call of the same in_mode
+    stores without a PReLU).  act: "none", "prelu" (alpha float32 [N]), "relu"
+    or "relu2".  mul, add: None (the operation is not performed) or the widened
+    float32 [M, N] operand.  Returns the float32 [M, N] value that the call
+    rounds once to its Y type."""
+    y = np.asarray(y32)
+    if y.dtype != np.float32 or y.ndim != 2:
+        raise TSGError(1, "epilogue_ref", "y32 must be a float32 [M, N] array")
+    if act not in _ACTS:
+        raise TSGError(1, "epilogue_ref", f"act must be one of {sorted(_ACTS)}, got {act!r}")
+    f = np.float32
+    for name, t in (("mul", mul), ("add", add)):
+        if t is not None and (np.asarray(t).dtype != np.float32 or np.asarray(t).shape != y.shape):
+            raise TSGError(1, "epilogue_ref", f"{name} must be None or a float32 {list(y.shape)} array")
+    with np.errstate(over="ignore", invalid="ignore"):
+        if act == "prelu":
+            alpha = np.asarray(alpha)
+            if alpha.dtype != np.float32 or alpha.shape != (y.shape[1],):
+                raise TSGError(1, "epilogue_ref", f"alpha must be a float32 [{y.shape[1]}] array")
+            a = np.where(y > 0, y, (alpha[None, :] * y).astype(f)).astype(f)
+        elif act in ("relu", "relu2"):
+            a = np.where(y > 0, y, np.where(y != y, y, f(0.0))).astype(f)  # -0 -> +0, a NaN stays
+            if act == "relu2":
+                a = (a * a).astype(f)
+        else:
+            a = y.copy()
+        if mul is not None:
+            a = (a * np.asarray(mul)).astype(f)
+        if add is not None:
+            a = (a + np.asarray(add)).astype(f)
+    return a
+
+
+def gemm_ex_check(desc, M: int, N: int, K: int) -> None:
+    """The host-side checks of the descriptor call (tsg_gemm_ex_check): no
+    device, no handle.  desc: a tsg_gemm_ex or None (a NULL descriptor).  Raises
+    TSGError naming the field that is wrong."""
+    _check(lib().tsg_gemm_ex_check(None if desc is None else C.byref(desc), M, N, K), "tsg_gemm_ex_check")
+
+
 class registered_host:
     """Context manager: page-locks numpy arrays for repeated host-pointer
     calls (tcsc_hip_host_register), unlocks them on exit."""
@@ -831,6 +898,95 @@ class TCSCDevice:
         gemm_torch_actquant.  Returns Y."""
         return self._torch_xy("gemm_torch_normquant", X, b, Y, alpha, out_dtype, narrow_y=True, col_scale=col_scale,
                               row_scale_out=row_scale_out, actquant=True, norm=True, gamma=gamma, eps=eps)
+
+    def gemm_dev_ex(self, desc, M: int, stream: int = 0) -> None:
+        """The descriptor call (tcsc_hip_gemm_dev_ex): desc is a tsg_gemm_ex of
+        device pointers that restates any of the device calls above (in_mode,
+        act) and adds the fused epilogue -- ReLU / ReLU^2, a gate multiply, a
+        residual add (epilogue_ref states the arithmetic)."""
+        _check(lib().tcsc_hip_gemm_dev_ex(self._h, None if desc is None else C.byref(desc), M, self.N, self.K,
+                                          stream or None), "tcsc_hip_gemm_dev_ex")
+
+    def gemm_torch_ex(self, X, b, Y=None, act="none", alpha=None, mul=None, add=None, out_dtype=None, row_scale=None,
+                      col_scale=None, quant=None, gamma=None, eps=None, row_scale_out=None):
+        """A projection with its fused epilogue in one call:
+        Y = cast(act(t + b) * mul + add), t the (scaled) chains of X.
+        quant: None (X as on gemm_torch_scaled, row_scale allowed), "act" (as on
+        gemm_torch_actquant) or "norm" (as on gemm_torch_normquant: gamma, eps).
+        act: "none", "prelu" (alpha), "relu" or "relu2".  mul, add: None or 2-D
+        [M, N] float32 / float16 / bfloat16 tensors on the handle's device with
+        unit column stride and any row stride >= N; the dtype picks the operand
+        type.  add=Y (or mul=Y) is the in-place form, h += proj(x).  The result
+        is epilogue_ref(...) of the fp32 call's value, rounded once to Y's
+        dtype, bit for bit.  Returns Y."""
+        import torch
+        where = "gemm_torch_ex"
+        dev = torch.device("cuda", self.device)
+        ytypes = {torch.float32: TSG_Y_F32, torch.float16: TSG_Y_F16, torch.bfloat16: TSG_Y_BF16}
+        xtypes = {torch.float32: TSG_X_F32, torch.float16: TSG_X_F16, torch.bfloat16: TSG_X_BF16,
+                  torch.int8: TSG_X_I8}
+        modes = {None: TSG_IN_PLAIN, "act": TSG_IN_ACTQUANT, "norm": TSG_IN_NORMQUANT}
+        if quant not in modes:
+            raise TSGError(1, where, f"quant must be None, 'act' or 'norm', got {quant!r}")
+        if act not in _ACTS:
+            raise TSGError(1, where, f"act must be one of {sorted(_ACTS)}, got {act!r}")
+        if (act == "prelu") != (alpha is not None):
+            raise TSGError(1, where, "alpha goes with act='prelu' and with no other act")
+        if not (isinstance(X, torch.Tensor) and X.dim() == 2 and X.shape[1] == self.K and X.dtype in xtypes
+                and X.device == dev and X.is_contiguous()):
+            raise TSGError(1, where, f"X must be a contiguous float32, float16, bfloat16 or int8 [M, {self.K}] "
+                                     f"tensor on {dev}")
+        M = X.shape[0]
+        for name, t, shape in (("b", b, (self.N,)), ("alpha", alpha, (self.N,)), ("row_scale", row_scale, (M,)),
+                               ("col_scale", col_scale, (self.N,)), ("row_scale_out", row_scale_out, (M,)),
+                               ("gamma", gamma, (self.K,))):
+            if t is None:
+                continue
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != dev or \
+                    not t.is_contiguous() or tuple(t.shape) != shape:
+                raise TSGError(1, where, f"{name} must be a contiguous float32 {list(shape)} tensor on {dev}")
+        if b is None:
+            raise TSGError(1, where, "b is required")
+        if out_dtype is not None and out_dtype not in ytypes:
+            raise TSGError(1, where, f"out_dtype must be float32, float16 or bfloat16, got {out_dtype}")
+        if Y is None:
+            Y = torch.empty((M, self.N), dtype=out_dtype or torch.float32, device=dev)
+
+        def rows(name, t):  # a [M, N] tensor with unit column stride -> its row stride in elements
+            if not isinstance(t, torch.Tensor) or t.dtype not in ytypes or t.device != dev or \
+                    tuple(t.shape) != (M, self.N):
+                got = (t.dtype, list(t.shape), t.device) if isinstance(t, torch.Tensor) else type(t)
+                raise TSGError(1, where, f"{name} must be a float32, float16 or bfloat16 [{M}, {self.N}] tensor on "
+                                         f"{dev}, got {got}")
+            if self.N > 1 and t.stride(1) != 1:
+                raise TSGError(1, where, f"{name}'s rows must be contiguous (stride(1) == 1), got {t.stride()}")
+            ld = self.N if M <= 1 else t.stride(0)  # one row has no next row
+            if ld < self.N:
+                raise TSGError(1, where, f"{name}'s rows overlap: stride(0) = {ld} < N = {self.N}")
+            return ld
+
+        d = tsg_gemm_ex()
+        d.in_mode, d.act = modes[quant], _ACTS[act]
+        d.dX, d.xtype = X.data_ptr(), xtypes[X.dtype]
+        d.ldY = rows("Y", Y)
+        d.dY, d.ytype = Y.data_ptr(), ytypes[Y.dtype]
+        if out_dtype is not None and Y.dtype != out_dtype:
+            raise TSGError(1, where, f"Y is {Y.dtype}, out_dtype is {out_dtype}: they must agree")
+        d.db = b.data_ptr()
+        d.dalpha = None if alpha is None else alpha.data_ptr()
+        d.drow_scale = None if row_scale is None else row_scale.data_ptr()
+        d.dcol_scale = None if col_scale is None else col_scale.data_ptr()
+        d.drow_scale_out = None if row_scale_out is None else row_scale_out.data_ptr()
+        d.dgamma = None if gamma is None else gamma.data_ptr()
+        d.eps = 0.0 if eps is None else float(eps)
+        if mul is not None:
+            d.ldmul = rows("mul", mul)
+            d.dmul, d.multype = mul.data_ptr(), ytypes[mul.dtype]
+        if add is not None:
+            d.ldadd = rows("add", add)
+            d.dadd, d.addtype = add.data_ptr(), ytypes[add.dtype]
+        self.gemm_dev_ex(d, M, torch.cuda.current_stream(dev).cuda_stream)
+        return Y
 
     def _torch_xy(self, where, X, b, Y, alpha, out_dtype, narrow_y, scaled=False, row_scale=None, col_scale=None,
                   row_scale_out=None, actquant=False, norm=False, gamma=None, eps=None):
