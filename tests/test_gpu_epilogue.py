@@ -300,14 +300,16 @@ def same_bytes(t, k):
 
 
 class Inputs:
-    """X, b, alpha and the scales of a case on the device, with copies to compare against."""
+    """X, b, alpha and the scales of a case on the device, with copies to compare against.
+    X: the case's X already on the device (a slice, say); extra: further (name,
+    tensor or None) pairs to keep a copy of (test_gpu_ex_fuzz.py: gamma)."""
 
-    def __init__(self, ec):
-        self.X, self.b, self.alpha = ec.Xt.cuda(), _dev(ec.b), _dev(ec.alpha)
+    def __init__(self, ec, X=None, extra=()):
+        self.X, self.b, self.alpha = ec.Xt.cuda() if X is None else X, _dev(ec.b), _dev(ec.alpha)
         self.rs = None if ec.rs is None else _dev(ec.rs)
         self.cs = None if ec.cs is None else _dev(ec.cs)
         self.named = [(n, t) for n, t in (("X", self.X), ("b", self.b), ("alpha", self.alpha),
-                                          ("row_scale", self.rs), ("col_scale", self.cs)) if t is not None]
+                                          ("row_scale", self.rs), ("col_scale", self.cs)) + tuple(extra) if t is not None]
         self.keep = [t.clone() for _, t in self.named]
 
     def assert_unchanged(self, what):
