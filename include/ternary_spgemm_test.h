@@ -139,6 +139,18 @@ int tsg_ell_build(const int32_t *col_start_pos, const int32_t *col_start_neg, co
                   int64_t ent_cap, int64_t *ent_len, uint32_t *tab, int64_t tab_cap, int64_t *tab_len, int32_t *C,
                   int32_t *nch, int32_t *xb);
 
+/* The rx kernel's block stream (tsg_tcsc_rx_kernel, the path of a W too large
+ * for one compiled image; csrc/tsg_internal.h RxImage): per (256-column tile,
+ * wave) the first dword of that wave's stream in wstart, the stream's blocks
+ * of 66 dwords in ent -- per step q = pass * nch + chunk one or more blocks
+ * {header, 0, 32 columns x 8 entry bytes}, the step's last block marked in
+ * bit 31 of its header, one all-zero block after the last stream -- and
+ * *nch, the 64-row K chunks.  Host only; NULL buffers query the lengths (in
+ * uint32). */
+int tsg_rx_build(const int32_t *col_start_pos, const int32_t *col_start_neg, const int32_t *row_index_pos,
+                 const int32_t *row_index_neg, int K, int N, uint32_t *wstart, int64_t wstart_cap,
+                 int64_t *wstart_len, uint32_t *ent, int64_t ent_cap, int64_t *ent_len, int32_t *nch);
+
 /* The 64-row image (no reference counterpart): one M row per
  * lane, 64-row M tiles, every nonzero one 4-byte VOP2 v_add_f32 / v_sub_f32,
  * X^T in the k-quad layout.  Same results bit for bit.  rows: 0 = automatic

@@ -548,3 +548,28 @@ extern "C" int tsg_ell_build(const int32_t *csp, const int32_t *csn, const int32
     if (tab) std::memcpy(tab, img.tab.data(), img.tab.size() * 4);
     return TSG_OK;
 }
+
+// Host-only view of the rx kernel's block stream (tests replay the kernel's
+// walk on the CPU).  NULL buffers query the lengths.
+extern "C" int tsg_rx_build(const int32_t *csp, const int32_t *csn, const int32_t *rip, const int32_t *rin, int K,
+                            int N, uint32_t *wstart, int64_t wstart_cap, int64_t *wstart_len, uint32_t *ent,
+                            int64_t ent_cap, int64_t *ent_len, int32_t *nch)
+{
+    const std::string e = tsg::validate_tcsc(csp, csn, rip, rin, K, N);
+    if (!e.empty()) {
+        g_tsg_host_err = "tsg_rx_build: " + e;
+        return TSG_ERR_ARG;
+    }
+    tsg::RxImage img;
+    tsg::build_rx_image(csp, csn, rip, rin, K, N, img);
+    if (wstart_len) *wstart_len = (int64_t)img.wstart.size();
+    if (ent_len) *ent_len = (int64_t)img.ent.size();
+    if (nch) *nch = img.nch;
+    if ((wstart && wstart_cap < (int64_t)img.wstart.size()) || (ent && ent_cap < (int64_t)img.ent.size())) {
+        g_tsg_host_err = "tsg_rx_build: buffer too small";
+        return TSG_ERR_ARG;
+    }
+    if (wstart) std::memcpy(wstart, img.wstart.data(), img.wstart.size() * 4);
+    if (ent) std::memcpy(ent, img.ent.data(), img.ent.size() * 4);
+    return TSG_OK;
+}

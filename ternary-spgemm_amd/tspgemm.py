@@ -47,7 +47,7 @@ EXPORTED_SYMBOLS = (
     "tcsc_hip_set_host_chunks", "tcsc_hip_host_chunk_rows", "tcsc_hip_call_image_bytes",
     "tcsc_hip_host_register", "tcsc_hip_host_unregister", "tcsc_hip_set_far", "tcsc_hip_call_far",
     "tsg_jit_codegen_far", "tsg_call_plan", "tsg_call_xtouch", "tsg_knob_check", "tcsc_hip_set_tile_rows", "tcsc_hip_call_tile_rows",
-    "tsg_jit_codegen64", "tsg_jit_codegen64h", "tcsc_hip_call_launches",
+    "tsg_jit_codegen64", "tsg_jit_codegen64h", "tcsc_hip_call_launches", "tsg_rx_build",
     "tcsc_hip_gemm_dev_ld", "tcsc_hip_gemm_prelu_dev_ld",
     "tcsc_hip_gemm_dev_x", "tcsc_hip_gemm_prelu_dev_x",
     "tcsc_hip_gemm_dev_xy", "tcsc_hip_gemm_prelu_dev_xy",
@@ -209,6 +209,8 @@ def lib() -> C.CDLL:
     L.tsg_ell_build.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int64,
                                 C.POINTER(C.c_int64), vp, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32),
                                 C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.tsg_rx_build.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, vp, C.c_int64, C.POINTER(C.c_int64), vp, C.c_int64,
+                               C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
     L.tsg_jit_tile_map.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.tcsc_hip_jit_width.argtypes = [H, C.c_int]
     L.tcsc_hip_jit_waves.argtypes = [H, C.c_int]
@@ -417,6 +419,22 @@ def ell_build(csp, csn, rip, rin, K: int, N: int, Cmax: int, MT: int, copies: in
            "tsg_ell_build")
     out = (ent.view(np.uint16), tab.reshape(-1, 2), c.value, nch.value)
     return out + (xb.value,) if with_xb else out
+
+
+def rx_build(csp, csn, rip, rin, K: int, N: int):
+    """Host view of the rx kernel's block stream (tsg_internal.h RxImage):
+    (wstart uint32[tiles * 8] = first dword of each (256-column tile, wave)
+    stream, ent uint32[] = the blocks of 66 dwords, nch = the 64-row K chunks)."""
+    csp, csn, rip, rin = _i32(csp), _i32(csn), _i32(rip), _i32(rin)
+    nw, ne, nch = C.c_int64(), C.c_int64(), C.c_int32()
+    L = lib()
+    _check(L.tsg_rx_build(_ptr(csp), _ptr(csn), _ptr(rip), _ptr(rin), K, N, None, 0, C.byref(nw), None, 0,
+                          C.byref(ne), C.byref(nch)), "tsg_rx_build")
+    wstart = np.empty(nw.value, np.uint32)
+    ent = np.empty(ne.value, np.uint32)
+    _check(L.tsg_rx_build(_ptr(csp), _ptr(csn), _ptr(rip), _ptr(rin), K, N, _ptr(wstart), nw.value, C.byref(nw),
+                          _ptr(ent), ne.value, C.byref(ne), C.byref(nch)), "tsg_rx_build")
+    return wstart, ent, nch.value
 
 
 def tcsc_to_blocked(csp, csn, rip, rin, K: int, N: int, B: int):
