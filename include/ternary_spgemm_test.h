@@ -183,6 +183,21 @@ int tsg_jit_codegen64h(const int32_t *col_start_pos, const int32_t *col_start_ne
                        int width, uint32_t *code, int64_t code_cap, int64_t *code_len,
                        uint32_t *wcode, int64_t wcode_cap, int64_t *wcode_len);
 
+/* The launch grid of a weight-compiled call.  tsg_call_grid
+ * (host only, no GPU): the workgroups a call with M rows launches on a
+ * plain-TCSC handle with K, N and nnz nonzeros whose tile rows (0, 64, 128) and
+ * stream width (0, 8 .. 128) are pinned as tcsc_hip_set_tile_rows /
+ * tcsc_hip_set_jit_width pin them and whose small-M walks are off; *tiles: the
+ * logical workgroup ids (M tiles x column tiles) they run.  The two are equal
+ * unless the call loops: with TSG_JIT_LOOP=G (1..4096; unset or 0: never) the
+ * 64-row image's 8-wave workgroups, given more ids than G, launch G
+ * workgroups, each running ids b, b + G, ...  Same results bit for bit.
+ * < 0: -TSG_ERR_ARG.  tcsc_hip_last_launch: the workgroups and, in *tiles (may
+ * be NULL), the logical ids of the handle's last weight-compiled launch, as
+ * they were passed to the runtime (0 before the first). */
+int tsg_call_grid(int K, int N, int64_t nnz, int M, int tile_rows, int width, int *tiles);
+int tcsc_hip_last_launch(const tsg_tcsc *h, int *tiles);
+
 /* The environment knobs (csrc/tsg_knobs.cpp): "" when every set TSG_* knob
  * has an accepted value, else the error registration reports (a set
  * TSG_JIT_DIAG is an error in the product build: its code variants give

@@ -47,6 +47,8 @@ struct tsg_tcsc {
     // pins the setters write and the images that failed to load
     tsg::PlanInput plan;
     int device = 0;
+    int cus = 0;                          // its compute units, read once at registration (TSG_JIT_DIAG=onetile)
+    int last_grid = 0, last_tiles = 0;    // workgroups and logical ids of the last weight-compiled launch (test hook)
     int64_t nnz_pos = 0, nnz_neg = 0;
     tsg::RxImage rimg;                    // device image of the rx kernel
     // jit kernel: one compiled image per (stream width, waves per workgroup)
@@ -574,9 +576,24 @@ int run_jit(tsg_tcsc *h, const CallPlan &p, const tsg_tcsc::JitVariant &jv, cons
     // the stream steps through X^T chunks with a 32-bit stride, and the grid
     // (one workgroup per M tile x column tile) must stay under 2^32 threads
     const int waves = jv.pair ? 2 * jv.waves : jv.waves;  // waves launched per workgroup
-    const int64_t wgs = (int64_t)(d.Mp / p.tile_m) * (jv.Npad / (jv.nw * jv.waves));
-    if ((int64_t)d.Mp * p.chunk * 4 >= (1ll << 31) || wgs * waves * 64 >= (1ll << 32))
+    // (waves: the pair factor included; the logical ids are 32-bit in the kernel)
+    // (= Mp / tile_m x Npad / cols, what launch_tcsc_jit derives for the kernel)
+    const int64_t wgs = tsg::jit_tiles(c.M, N, p.tile_m, jv.nw * jv.waves);
+    if ((int64_t)d.Mp * p.chunk * 4 >= (1ll << 31) || wgs * waves * 64 >= (1ll << 32) || wgs >= (1ll << 31))
         return fail(TSG_ERR_ARG, "M=" + std::to_string(c.M) + " is too large for one jit launch; split the rows");
+    // the looping launch (TSG_JIT_LOOP; tsg_plan.cpp loop_wgs): that many
+    // workgroups, each running every loop-th logical id
+    int loop = jv.pair ? 0 : tsg::loop_wgs(p.shape, wgs);
+    int lflags = 0;
+#ifdef TSG_DIAG
+    if (const char *dv = tsg::knob_value("TSG_JIT_DIAG")) {  // results WRONG (timing studies)
+        if (std::strstr(dv, "nostore")) lflags |= tsg::kJitDiagNoStore;
+        if (std::strstr(dv, "onetile")) {  // the first round alone
+            lflags |= tsg::kJitDiagOneTile;
+            loop = (int)std::min<int64_t>(wgs, std::max(h->cus / 8 * 8, 8));
+        }
+    }
+#endif
     // the 64-row image stages straight from row-major X (no X^T pass, no work
     // buffer) when every row starts 16-B aligned and the offsets fit 32 bits
     // (the image's DMA reads fp32: an X of another type is always staged, by
@@ -617,11 +634,14 @@ int run_jit(tsg_tcsc *h, const CallPlan &p, const tsg_tcsc::JitVariant &jv, cons
     int slot;
     rc = timing_begin(h, c.capturing, c.s, slot);
     if (rc) return rc;
+    int launched[2] = {0, 0};
     if (tsg::launch_tcsc_jit(jv.mod, direct ? static_cast<const float *>(c.dX) : h->d_work, d.Mp, jv.d_wcode, c.db,
                              c.dalpha, drs, c.dcs, c.ep, c.dY, c.ytype, c.ldY, c.M, N,
                              jv.Npad, jv.nch, c.prelu ? 1 : 0, h->d_status, jv.nw * jv.waves, waves, p.gn, p.gm, p.tmask,
-                             c.s, p.tile_m, direct ? K : 0, lastadj, p.xtouch, p.tnear) != 0)
+                             c.s, p.tile_m, direct ? K : 0, lastadj, p.xtouch, p.tnear, loop, lflags, launched) != 0)
         return fail(TSG_ERR_HIP, std::string("tcsc launch: ") + hipGetErrorString(hipGetLastError()));
+    h->last_grid = launched[0];
+    h->last_tiles = launched[1];
     rc = timing_end(h, slot, c.s);
     if (rc || direct) return rc;
     return work_end(h, c);
@@ -918,6 +938,10 @@ int create_impl(const int32_t *csp, const int32_t *csn, const int32_t *rip, cons
     h->plan.N = N;
     h->plan.B = B;
     h->device = device;
+    if (hipDeviceGetAttribute(&h->cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) {
+        (void)hipGetLastError();
+        h->cus = 0;  // (only the diagnostic one-round launch reads it)
+    }
     {
         DeviceGuard g0(device);
         if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
@@ -1319,6 +1343,51 @@ extern "C" int tsg_call_plan(int K, int N, int64_t nnz, int M, int *kernel, int 
     *gm = p.gm;
     *tmask = p.tmask;
     return TSG_OK;
+}
+
+// The launch grid of an M-row weight-compiled call of such a handle, with
+// tile_rows and width pinned as tcsc_hip_set_tile_rows / _set_jit_width pin
+// them (0: automatic): the workgroups run_jit asks launch_tcsc_jit for (the
+// same jit_tiles and loop_wgs, tsg_plan.cpp), and in *tiles the logical ids
+// they run.  Host only; tcsc_hip_last_launch reports what a call launched.
+extern "C" int tsg_call_grid(int K, int N, int64_t nnz, int M, int tile_rows, int width, int *tiles)
+{
+    if (K < 0 || N <= 0 || nnz < 0 || nnz > (int64_t)K * N || M <= 0 || !tiles ||
+        (tile_rows != 0 && tile_rows != 64 && tile_rows != 128) ||
+        (width != 0 && width != 8 && width != 16 && width != 32 && width != 64 && width != 128) ||
+        (width == 128 && tile_rows == 128)) {
+        g_tsg_host_err = "tsg_call_grid: bad arguments";
+        return -TSG_ERR_ARG;
+    }
+    const std::string ke = tsg::knob_check();
+    if (!ke.empty()) {
+        g_tsg_host_err = "tsg_call_grid: " + ke;
+        return -TSG_ERR_ARG;
+    }
+    tsg::PlanInput in = plain_input(K, N, nnz);
+    in.tile_rows = tile_rows;
+    in.jit_force = width;
+    in.small_m = 1;
+    const CallPlan p = tsg::plan_call(in, M);
+    if (!p.is_jit()) {
+        g_tsg_host_err = "tsg_call_grid: not a weight-compiled call";
+        return -TSG_ERR_ARG;
+    }
+    const int64_t t = tsg::jit_tiles(M, N, p.tile_m, p.shape.nw * p.shape.waves);
+    const int g = tsg::loop_wgs(p.shape, t);
+    *tiles = (int)t;
+    return g ? g : (int)t;
+}
+
+// Workgroups of the handle's last weight-compiled launch and, in *tiles, the
+// logical ids it passed to the kernel: what launch_tcsc_jit handed to the
+// runtime (0 before the first such launch).
+extern "C" int tcsc_hip_last_launch(const tsg_tcsc *h, int *tiles)
+{
+    if (!h) return 0;
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (tiles) *tiles = h->last_tiles;
+    return h->last_grid;
 }
 
 // Whether an M-row call of a plain-TCSC handle with K, N and nnz nonzeros

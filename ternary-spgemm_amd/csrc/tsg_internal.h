@@ -285,7 +285,15 @@ int launch_tcsc_jit(const JitModule &jm, const float *XT, int Mp, const uint32_t
                     const float *b, const float *alpha, const float *rs, const float *cs, const Epi &ep, void *Y, int ytype,
                     int64_t ldY, int M, int N, int Npad, int nch, int prelu, uint32_t *status, int tile_cols,
                     int waves, int gn, int gm, int tmask, void *stream, int tile_m = kJitTileM, int xrow = 0, int lastadj = 0, int xtouch = 0,
-                    int tnear = 0);
+                    int tnear = 0, int loop_wgs = 0, int lflags = 0, int *launched = nullptr);
+// loop_wgs > 0: that many workgroups, each looping over the logical ids b,
+// b + loop_wgs, ... (the 64-row image's 8-wave dispatcher only; tsg_plan.h
+// loop_wgs); 0: one workgroup per id.  lflags (diagnostic build only,
+// TSG_JIT_DIAG; results WRONG): nostore -- the dispatcher skips its epilogue
+// (bit 30 of its lstep argument); onetile -- the launch covers only its first
+// loop_wgs logical ids.  launched (may be null): {workgroups, logical ids} of
+// the launch as passed to the runtime and the kernel
+constexpr int kJitDiagNoStore = 1 << 30, kJitDiagOneTile = 1 << 29;
 int launch_jit_probe(const JitModule &jm, uint32_t *status, void *stream);
 
 // ---------------------------------------------------------------------------

@@ -938,6 +938,8 @@ constexpr const char *kJitYtypeMarker = "tsg_jit_args_ytype";
 constexpr const char *kJitScaleMarker = "tsg_jit_args_scale";
 // ... and with the fused epilogue (Epi, by value) after them
 constexpr const char *kJitEpiMarker = "tsg_jit_args_epi";
+// ... and with the two loop arguments (ltiles, lstep) after it
+constexpr const char *kJitLoopMarker = "tsg_jit_args_loop";
 
 // The dispatcher of a stream width: tsg_jit.co (kJitNW columns per wave) or
 // tsg_jit_w<nw>.co (same kernel built with TSG_JIT_NW=nw, Makefile); 4-wave
@@ -1099,6 +1101,13 @@ std::string JitModule::load(const std::vector<uint32_t> &code, int nw, int waves
         return std::string("jit template ") + template_name(nw, waves, r64, half, pair) +
                " predates the dispatcher's epilogue argument (no " + kJitEpiMarker + "); rebuild it";
     }
+    // and for the two loop arguments after the epilogue
+    if (hipModuleGetFunction(&mark, m, kJitLoopMarker) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipModuleUnload(m);
+        return std::string("jit template ") + template_name(nw, waves, r64, half, pair) +
+               " predates the dispatcher's loop arguments (no " + kJitLoopMarker + "); rebuild it";
+    }
     module = m;
     function = fn;
     probe = pf;
@@ -1124,17 +1133,30 @@ int launch_jit_probe(const JitModule &jm, uint32_t *status, void *stream)
 int launch_tcsc_jit(const JitModule &jm, const float *XT, int Mp, const uint32_t *wcode, const float *b,
                     const float *alpha, const float *rs, const float *cs, const Epi &ep, void *Y, int ytype,
                     int64_t ldY, int M, int N, int Npad, int nch, int prelu, uint32_t *status, int tile_cols, int waves, int gn, int gm,
-                    int tmask, void *stream, int tile_m, int xrow, int lastadj, int xtouch, int tnear)
+                    int tmask, void *stream, int tile_m, int xrow, int lastadj, int xtouch, int tnear, int loop_wgs,
+                    int lflags, int *launched)
 {
     int mtiles = Mp / tile_m, ntiles = Npad / tile_cols;
+    // one workgroup per logical id, or loop_wgs workgroups that stride over
+    // the ids (the looping dispatcher, tsg_jit_kernel.hip; tsg_plan.cpp loop_wgs)
+    int ltiles = mtiles * ntiles;
+    const int grid = loop_wgs > 0 && loop_wgs < ltiles ? loop_wgs : ltiles;
+    int lstep = grid;
+#ifdef TSG_DIAG
+    if (lflags & kJitDiagOneTile) ltiles = grid;  // one round of the same shape (results WRONG)
+    lstep |= lflags & kJitDiagNoStore;
+#else
+    (void)lflags;
+#endif
     if (rs || cs) ytype |= kYScaled;  // the dispatcher's one test ahead of its fp32 path (tsg_jit_kernel.hip)
     if (ep.on()) ytype |= kYEpi;      // likewise: a call with a fused epilogue (tsg_epilogue.h)
     void *params[] = {(void *)&XT, (void *)&Mp, (void *)&wcode, (void *)&b, (void *)&alpha, (void *)&Y,
                       (void *)&M, (void *)&N, (void *)&nch, (void *)&mtiles, (void *)&ntiles, (void *)&prelu,
                       (void *)&status, (void *)&gn, (void *)&gm, (void *)&tmask, (void *)&xrow, (void *)&lastadj,
                       (void *)&xtouch, (void *)&tnear, (void *)&ldY, (void *)&ytype, (void *)&rs, (void *)&cs,
-                      (void *)&ep};
-    hipError_t e = hipModuleLaunchKernel((hipFunction_t)jm.function, (unsigned)(mtiles * ntiles), 1, 1,
+                      (void *)&ep, (void *)&ltiles, (void *)&lstep};
+    if (launched) launched[0] = grid, launched[1] = ltiles;
+    hipError_t e = hipModuleLaunchKernel((hipFunction_t)jm.function, (unsigned)grid, 1, 1,
                                          (unsigned)waves * 64u, 1, 1, 0, (hipStream_t)stream, params, nullptr);
     return e == hipSuccess ? 0 : -1;
 }

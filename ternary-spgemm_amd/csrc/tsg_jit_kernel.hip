@@ -43,6 +43,7 @@
 //   s[92:93] region base, s[94:95] return address.
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdint>
 
 #include "tsg_epilogue.h"
@@ -96,6 +97,13 @@ static_assert(!kJHalf || (kJRows64 && TSG_JIT_WAVES == 4), "the half ring is a 4
 static_assert(!kJPair || (kJRows64 && TSG_JIT_WAVES == 4 && !kJHalf), "wave pairs run the 4-wave 64-row image");
 static_assert(kJNW == 64 || kJNW == 32 || kJNW == 16 || kJNW == 8 || (kJRows64 && kJNW == 128), "stream width");
 static_assert(kJWaves == 8 || (kJWaves == 4 && kJNW < 64), "waves per workgroup");
+// The looping dispatcher: the 64-row image's 8-wave
+// workgroups run logical ids L = blockIdx.x, + lstep, ... below ltiles, each
+// through tsg_jit_tile.  Every other code object runs its one id and ignores
+// the two arguments (the host launches one workgroup per id there).
+#define TSG_JIT_LOOP (TSG_JIT_ROWS64 && TSG_JIT_WAVES == 8)  // (the half ring and the pairs have 4-wave streams)
+constexpr bool kJLoop = TSG_JIT_LOOP;
+constexpr int kJDiagNoStore = 1 << 30;  // lstep (TSG_DIAG builds only): skip the epilogue (results WRONG)
 constexpr int kJTileM = kJRows64 ? 64 : 128;
 constexpr int kJRowsPerLane = kJTileM / 64;
 constexpr int kJTileCols = kJWaves * kJNW;
@@ -146,6 +154,61 @@ typedef float F32x8 __attribute__((ext_vector_type(8)));
         "v100", "v101", "v102", "v103", "v107", "s84", "s85", "s86", "s88", "s89", "s94", "s95", \
         "scc", "memory"
 
+#if TSG_JIT_LOOP
+// The looping dispatcher reads its arguments from the kernel-argument segment
+// per tile -- once before the stream, once after it -- through a pointer the
+// compiler cannot see through.  Read as formal parameters they are loop
+// invariants: the compiler keeps them, and what it hoists of the set-up and
+// the epilogue, in registers across the stream, and the width-128 build, which
+// has 20 VGPRs and few SGPRs to spare there, spills (200 SGPRs to VGPR lanes,
+// one VGPR to scratch).  This struct is the dispatcher's argument list as the
+// segment lays it out: every argument at its natural alignment, in order (the
+// kernel checks the last two against its formal parameters before it loops).
+// The read-only arrays are typed as constant memory, so their uniform loads
+// stay scalar loads without the formal parameters' __restrict__, and Y as
+// global memory.
+#define TSG_AS(n) __attribute__((address_space(n)))
+struct JitArgs {
+    const float *XT;
+    int Mp;
+    const TSG_AS(4) uint32_t *wcode;
+    const TSG_AS(4) float *b, *alpha;
+    TSG_AS(1) float *Y;
+    int M, N, nch, mtiles, ntiles, prelu;
+    uint32_t *status;
+    int gn, gm, tmask, xrow, lastadj, xtouch, tnear;
+    int64_t ldY;
+    int ytype;
+    const TSG_AS(4) float *rs, *cs;
+    tsg::Epi ep;
+    int ltiles, lstep;
+};
+// the segment's offsets, spelled out: an argument added to or moved in the
+// formal list (below) and launch_tcsc_jit's params[] changes these with it
+static_assert(offsetof(JitArgs, XT) == 0 && offsetof(JitArgs, Mp) == 8 && offsetof(JitArgs, wcode) == 16 &&
+                  offsetof(JitArgs, b) == 24 && offsetof(JitArgs, alpha) == 32 && offsetof(JitArgs, Y) == 40 &&
+                  offsetof(JitArgs, M) == 48 && offsetof(JitArgs, N) == 52 && offsetof(JitArgs, nch) == 56 &&
+                  offsetof(JitArgs, mtiles) == 60 && offsetof(JitArgs, ntiles) == 64 &&
+                  offsetof(JitArgs, prelu) == 68 && offsetof(JitArgs, status) == 72 && offsetof(JitArgs, gn) == 80 &&
+                  offsetof(JitArgs, gm) == 84 && offsetof(JitArgs, tmask) == 88 && offsetof(JitArgs, xrow) == 92 &&
+                  offsetof(JitArgs, lastadj) == 96 && offsetof(JitArgs, xtouch) == 100 &&
+                  offsetof(JitArgs, tnear) == 104 && offsetof(JitArgs, ldY) == 112 && offsetof(JitArgs, ytype) == 120 &&
+                  offsetof(JitArgs, rs) == 128 && offsetof(JitArgs, cs) == 136 && offsetof(JitArgs, ep) == 144 &&
+                  offsetof(JitArgs, ltiles) == 144 + sizeof(tsg::Epi) &&
+                  offsetof(JitArgs, lstep) == 148 + sizeof(tsg::Epi) && sizeof(JitArgs) == 152 + sizeof(tsg::Epi),
+              "JitArgs is the dispatcher's kernel-argument segment");
+typedef const TSG_AS(4) JitArgs *JitArgsPtr;
+typedef const TSG_AS(4) float *JitCF;  // a read-only float argument
+__device__ __forceinline__ JitArgsPtr jit_args()
+{
+    JitArgsPtr p = (JitArgsPtr)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return p;
+}
+#else
+typedef const float *JitCF;
+#endif
+
 }  // namespace
 
 // Probe (tsg_capi.cpp ensure_jit_variant, once per loaded image, never in a
@@ -186,17 +249,24 @@ extern "C" __global__ __launch_bounds__(64) void tsg_jit_args_scale() {}
 // residual operand with their row strides, and the bits), with the kYEpi flag
 // in ytype when the call has one (looked up last)
 extern "C" __global__ __launch_bounds__(64) void tsg_jit_args_epi() {}
+// ... and for the two loop arguments after it: ltiles, the logical ids of the
+// launch, and lstep, the stride between a workgroup's ids (looked up last)
+extern "C" __global__ __launch_bounds__(64) void tsg_jit_args_loop() {}
 
 // (the half ring: two workgroups per CU, so at most 256 VGPRs -- two waves per SIMD)
+// The argument list lives in three places that change together: here,
+// JitArgs above (the looping builds read the segment through it) and
+// launch_tcsc_jit's params[] (tsg_jit.cpp).
 extern "C" __global__ __launch_bounds__(kJThreads, kJHalf ? 2 : 1) void TSG_JIT_KERNEL_NAME(
     const float *__restrict__ XT, int Mp, const uint32_t *__restrict__ wcode,
     const float *__restrict__ b, const float *__restrict__ alpha, float *__restrict__ Y, int M, int N,
     int nch, int mtiles, int ntiles, int prelu, uint32_t *__restrict__ status, int gn, int gm,
     int tmask, int xrow, int lastadj, int xtouch, int tnear, int64_t ldY, int ytype,
-    const float *__restrict__ rs, const float *__restrict__ cs, tsg::Epi ep)
+    const float *__restrict__ rs, const float *__restrict__ cs, tsg::Epi ep, int ltiles, int lstep)
 {
     __shared__ __attribute__((aligned(16))) char lds[kJRing * kJBufBytes];
-    const int tid = threadIdx.x, lane = tid & 63;
+    const int tid = threadIdx.x;
+    [[maybe_unused]] const int lane0 = tid & 63;
     // LDS is only addressed from the generated code, at absolute offsets from
     // 0 (the only LDS object): this use keeps the allocation in the descriptor
     asm volatile("; lds %0" ::"v"(lds));
@@ -223,10 +293,34 @@ extern "C" __global__ __launch_bounds__(kJThreads, kJHalf ? 2 : 1) void TSG_JIT_
         return;
     }
 
+#if TSG_JIT_LOOP
+    // the argument struct is the segment (JitArgs above), or nothing loops
+    if (jit_args()->ltiles != ltiles || jit_args()->lstep != lstep) {
+        if (blockIdx.x == 0 && tid == 0) status[0] = 1u;
+        return;
+    }
+#endif
+    // One pass of this loop per logical id (kJLoop; every other code object:
+    // one pass, on its formal parameters).  Nothing but L is carried from a
+    // tile to the next: the arguments are loaded (JitArgs above; the names
+    // below shadow the formal parameters) and the lane index is computed per
+    // pass, so that nothing derived from them is kept across the stream.
+    for (int L = blockIdx.x;;) {
+#if TSG_JIT_LOOP
+    const JitArgsPtr ka = jit_args();
+    const float *const XT = ka->XT;
+    const TSG_AS(4) uint32_t *const wcode = ka->wcode;
+    const int Mp = ka->Mp, M = ka->M, mtiles = ka->mtiles, ntiles = ka->ntiles, gn = ka->gn, gm = ka->gm,
+              tmask = ka->tmask, xrow = ka->xrow, lastadj = ka->lastadj, xtouch = ka->xtouch, tnear = ka->tnear;
+    int lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));  // = tid & 63
+    asm volatile("" : "+v"(lane));
+#else
+    const int lane = lane0;
+#endif
     // tile map (tsg_jit_map.h): gn column tiles x gm M tiles per XCD group,
     // chosen per call by the host (tsg_plan.cpp pick_jit_map)
     int nt, mt;
-    tsg_jit_tile(blockIdx.x, mtiles, ntiles, gn, gm, nt, mt);
+    tsg_jit_tile(L, mtiles, ntiles, gn, gm, nt, mt);
     const int m0 = mt * kJTileM;
     const int stream = wave;  // the wave's column stream
     const int ncol0 = nt * kJTileCols + stream * kJNW;
@@ -401,9 +495,29 @@ extern "C" __global__ __launch_bounds__(kJThreads, kJHalf ? 2 : 1) void TSG_JIT_
 #endif
 #undef TSG_JIT_CALL
 
-    if (ncol0 >= N) return;
-    if (kJPair && (lane >> 5) != rhalf) return;  // the pair's other wave holds these rows
-    if (__builtin_expect(ytype != tsg::kYF32, 0)) {  // (out of line: the fp32 path keeps its layout)
+    // the tile's epilogue; skipped, never left (a wave that returned while the
+    // others loop would hang the workgroup at the next barrier), by a wave
+    // whose columns lie past N and by the lanes of a pair's other wave, which
+    // holds their rows
+    {
+#if TSG_JIT_LOOP
+    // (after the stream: the epilogue's arguments and the lane index, again)
+    const JitArgsPtr ke = jit_args();
+    const JitCF b = ke->b, alpha = ke->alpha, rs = ke->rs, cs = ke->cs;
+    float *const Y = (float *)ke->Y;
+    const int M = ke->M, N = ke->N, prelu = ke->prelu, ytype = ke->ytype;
+    const int64_t ldY = ke->ldY;
+    tsg::Epi ep;
+    ep.mul = ke->ep.mul, ep.ldmul = ke->ep.ldmul, ep.add = ke->ep.add, ep.ldadd = ke->ep.ldadd, ep.bits = ke->ep.bits;
+    int lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    asm volatile("" : "+v"(lane));
+#endif
+    bool store = ncol0 < N && !(kJPair && (lane >> 5) != rhalf);
+#ifdef TSG_DIAG
+    if (lstep & kJDiagNoStore) store = false;  // TSG_JIT_DIAG=nostore (results WRONG)
+#endif
+    if (!store) {
+    } else if (__builtin_expect(ytype != tsg::kYF32, 0)) {  // (out of line: the fp32 path keeps its layout)
         if (ytype & tsg::kYEpi) {
             // a call with a fused epilogue (uniform; tsg_epilogue.h): the
             // scaled branch below -- a missing scale's multiply not performed,
@@ -419,7 +533,7 @@ extern "C" __global__ __launch_bounds__(kJThreads, kJHalf ? 2 : 1) void TSG_JIT_
                 if (m >= M) continue;
                 // this branch's own copies, fenced like the ones below
                 int nc0 = ncol0;
-                const float *bs = b, *alphas = alpha, *rss = rs, *css = cs;
+                JitCF bs = b, alphas = alpha, rss = rs, css = cs;
                 asm volatile("" : "+s"(nc0), "+s"(bs), "+s"(alphas), "+s"(rss), "+s"(css));
                 const bool has_rs = rss != nullptr, has_cs = css != nullptr;
                 const float rm = has_rs ? rss[m] : 0.0f;
@@ -430,9 +544,7 @@ extern "C" __global__ __launch_bounds__(kJThreads, kJHalf ? 2 : 1) void TSG_JIT_
                     return y;
                 });
             }
-            return;
-        }
-        if (ytype & tsg::kYScaled) {
+        } else if (ytype & tsg::kYScaled) {
             // a scaled call (uniform; tsg_scale.h): ((chain * rs[m]) * cs[n]) +
             // b[n], three roundings, then the PReLU and the store of any Y type
             // (the flag's other bits).  The host sets the flag in ytype when it
@@ -448,7 +560,7 @@ extern "C" __global__ __launch_bounds__(kJThreads, kJHalf ? 2 : 1) void TSG_JIT_
                 if (m >= M) continue;
                 // this branch's own copies, fenced like the 16-bit ones below
                 int nc0 = ncol0;
-                const float *bs = b, *alphas = alpha, *rss = rs, *css = cs;
+                JitCF bs = b, alphas = alpha, rss = rs, css = cs;
                 asm volatile("" : "+s"(nc0), "+s"(bs), "+s"(alphas), "+s"(rss), "+s"(css));
                 const bool has_rs = rss != nullptr, has_cs = css != nullptr;
                 const float rm = has_rs ? rss[m] : 0.0f;
@@ -459,8 +571,7 @@ extern "C" __global__ __launch_bounds__(kJThreads, kJHalf ? 2 : 1) void TSG_JIT_
                     return y;
                 });
             }
-            return;
-        }
+        } else {
         // a 16-bit Y (uniform): the same fp32 value, rounded once and stored
         // 8 columns at a time (tsg_ytype.h); ldY counts 16-bit elements
 #pragma unroll
@@ -472,7 +583,7 @@ extern "C" __global__ __launch_bounds__(kJThreads, kJHalf ? 2 : 1) void TSG_JIT_
             // once for both branches, ahead of them, and keep it in scalar
             // registers the fp32 path then has to spill around
             int nc0 = ncol0;
-            const float *b16 = b, *alpha16 = alpha;
+            JitCF b16 = b, alpha16 = alpha;
             asm volatile("" : "+s"(nc0), "+s"(b16), "+s"(alpha16));
             tsg::ystore_seg<kJNW>(Y, ytype, (size_t)m * (size_t)ldY + nc0, N - nc0, [&](int c) {
                 const int n = nc0 + c < N ? nc0 + c : N - 1;
@@ -481,8 +592,8 @@ extern "C" __global__ __launch_bounds__(kJThreads, kJHalf ? 2 : 1) void TSG_JIT_
                 return y;
             });
         }
-        return;
-    }
+        }
+    } else {
 #pragma unroll
     for (int r = 0; r < kJRowsPerLane; r++) {
         const int m = m0 + kJRowsPerLane * lane + r;
@@ -506,5 +617,19 @@ extern "C" __global__ __launch_bounds__(kJThreads, kJHalf ? 2 : 1) void TSG_JIT_
             for (int c = 0; c < kJNW; c++)
                 if (ncol0 + c < N) yrow[c] = v[c];
         }
+    }
+    }
+    }
+    // the workgroup's next id.  The stores above are not waited for: the next
+    // stream's first vmcnt wait (its prologue, before it reads LDS) orders
+    // after them.  One barrier before the next stream: a wave must not stage
+    // the next tile's first chunks into ring buffers 0 and 1 while another
+    // wave still reads this tile's last chunks there (every wave reaches it:
+    // nothing above returns)
+    if (!kJLoop) break;
+    const int step = lstep & ~kJDiagNoStore;
+    if (step <= 0 || L >= ltiles - step) break;  // (a stride of 0 never loops)
+    L += step;
+    __builtin_amdgcn_s_barrier();
     }
 }

@@ -99,7 +99,7 @@ bool diag_ok(const char *v)
 {
     for (const auto &s : fields(v))
         if (!one_of(s.c_str(), {"nobar", "nodma", "notouch", "nolgkm", "noreads", "novm", "samecode", "samewave",
-                                "pairwave", "simdpair", "balance4", "balance1", "anti4"}))
+                                "pairwave", "simdpair", "balance4", "balance1", "anti4", "nostore", "onetile"}))
             return false;
     return true;
 }
@@ -138,6 +138,8 @@ const Knob kKnobs[] = {
     {"TSG_JIT_TROLL", "0..8 (rolling code touches, 8-KiB windows ahead)", [](const char *v) { return int_in(v, 0, 8); }},
     {"TSG_JIT_MIX", "reads,dma (0|1 each)",
      [](const char *v) { return one_of(v, {"0,0", "0,1", "1,0", "1,1"}); }},
+    {"TSG_JIT_LOOP", "0 (never loop, the default) | 1..4096 (workgroups of a looping launch)",
+     [](const char *v) { return int_in(v, 0, 4096); }},
     {"TSG_JIT_DIR", "a directory", [](const char *v) { return *v != '\0'; }},
     {"TSG_ELL_PC", "0 | 1", [](const char *v) { return one_of(v, {"0", "1"}); }},
     {"TSG_ELL_MAXM", "0..1024", [](const char *v) { return int_in(v, 0, 1024); }},
@@ -150,7 +152,7 @@ const Knob kKnobs[] = {
     {"TSG_ELL_WPG", "4 | 8 | 16", [](const char *v) { return one_of(v, {"4", "8", "16"}); }},
     {"TSG_ELL_SCHED", "0 | 1", [](const char *v) { return one_of(v, {"0", "1"}); }},
 #ifdef TSG_DIAG
-    {"TSG_JIT_DIAG", "nobar,nodma,notouch,nolgkm,noreads,novm,samecode,samewave,pairwave,simdpair,balance4,balance1,anti4", diag_ok},
+    {"TSG_JIT_DIAG", "nobar,nodma,notouch,nolgkm,noreads,novm,samecode,samewave,pairwave,simdpair,balance4,balance1,anti4,nostore,onetile", diag_ok},
 #endif
 };
 

@@ -568,6 +568,21 @@ bool x_direct(const PlanInput &in, const JitShape &sh, int piece_rows, bool x_al
     return on && x_direct_shape_ok(in.K, piece_rows) && x_aligned && x_direct_offsets_ok(M, in.K);
 }
 
+int64_t jit_tiles(int M, int N, int tile_m, int cols)
+{
+    return (int64_t)((std::max(M, 1) + tile_m - 1) / tile_m) * ((N + cols - 1) / cols);
+}
+
+// Not automatic: no call loops unless TSG_JIT_LOOP names a grid (DESIGN.md
+// 4.2 has the A/B that decides this, profiles/loop_ab.jsonl).
+int loop_wgs(const JitShape &sh, int64_t tiles)
+{
+    if (!sh.r64 || sh.half || sh.waves != kJitWaves) return 0;
+    const char *e = knob_value("TSG_JIT_LOOP");
+    const int g = e ? atoi(e) : 0;  // 0: never; else the grid as given
+    return g > 0 && tiles > g ? g : 0;
+}
+
 // A call may fall back from an image that cannot be loaded to the 128-row
 // 64 x 8 image when nothing pinned its image or shape (a pinned request fails
 // loudly instead: TSG_ERR_HIP).

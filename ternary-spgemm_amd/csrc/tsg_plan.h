@@ -56,6 +56,20 @@ struct CallPlan {
 
 CallPlan plan_call(const PlanInput &in, int M);
 
+// Logical workgroup ids of a weight-compiled call: M tiles x column tiles
+// (cols = stream width x streams per workgroup)
+int64_t jit_tiles(int M, int N, int tile_m, int cols);
+
+// The looping launch (tsg_jit_kernel.hip): the workgroups G a
+// call on the image `sh` with `tiles` logical ids launches when each is to
+// run several ids -- b, b + G, ... --; 0: one workgroup per id.  Only the
+// 64-row image's 8-wave workgroups can loop, and only with more ids than G.
+// G is TSG_JIT_LOOP (1..4096, read per call; a multiple of 8 keeps every id
+// on its XCD, tsg_jit_map.h; tests loop tiny shapes with small values); unset
+// or 0, no call loops.  A launch decision, not part of the CallPlan: the tile
+// map, the touch mask and the image are those of the unlooped call.
+int loop_wgs(const JitShape &sh, int64_t tiles);
+
 // Whether a call on the image `sh` reads X directly (no X^T pass; 64-row
 // image only): depends on the call's X (rows 16-B aligned) and on the built
 // image's layout -- piece_rows, or -1 for an image not built yet (then the

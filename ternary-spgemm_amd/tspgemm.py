@@ -54,7 +54,7 @@ EXPORTED_SYMBOLS = (
     "tcsc_hip_gemm_dev_scaled", "tcsc_hip_gemm_prelu_dev_scaled",
     "tcsc_hip_gemm_dev_actquant", "tcsc_hip_gemm_prelu_dev_actquant",
     "tcsc_hip_gemm_dev_normquant", "tcsc_hip_gemm_prelu_dev_normquant",
-    "tcsc_hip_gemm_dev_ex", "tsg_gemm_ex_check",
+    "tcsc_hip_gemm_dev_ex", "tsg_gemm_ex_check", "tsg_call_grid", "tcsc_hip_last_launch",
 )
 
 # enum tsg_xtype (include/ternary_spgemm.h): element type of X on the _x calls
@@ -194,6 +194,8 @@ def lib() -> C.CDLL:
                                      C.POINTER(C.c_int64), vp, C.c_int64, C.POINTER(C.c_int64)]
     L.tsg_call_plan.argtypes = [C.c_int, C.c_int, C.c_int64, C.c_int] + [C.POINTER(C.c_int)] * 7
     L.tsg_call_xtouch.argtypes = [C.c_int, C.c_int, C.c_int64, C.c_int]
+    L.tsg_call_grid.argtypes = [C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
+    L.tcsc_hip_last_launch.argtypes = [H, C.POINTER(C.c_int)]
     L.tcsc_hip_call_far.argtypes = [H, C.c_int]
     L.tsg_jit_codegen_far.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, vp, C.c_int64,
                                       C.POINTER(C.c_int64), vp, C.c_int64, C.POINTER(C.c_int64)]
@@ -392,6 +394,17 @@ def call_xtouch(K: int, N: int, nnz: int, M: int) -> bool:
     r = lib().tsg_call_xtouch(K, N, nnz, M)
     _check(min(r, 0), "tsg_call_xtouch")
     return bool(r)
+
+
+def call_grid(K: int, N: int, nnz: int, M: int, tile_rows: int = 0, width: int = 0):
+    """(workgroups launched, logical workgroup ids) of an M-row weight-compiled
+    call with the tile rows and stream width pinned (0: automatic)
+    (tsg_call_grid, host only): the first is smaller when TSG_JIT_LOOP makes
+    the call loop its workgroups over the ids."""
+    tiles = C.c_int()
+    r = lib().tsg_call_grid(K, N, nnz, M, tile_rows, width, C.byref(tiles))
+    _check(-r if r < 0 else 0, "tsg_call_grid")
+    return r, tiles.value
 
 
 def jit_tile_map(L: int, mtiles: int, ntiles: int, gn: int, gm: int):
@@ -1184,6 +1197,12 @@ class TCSCDevice:
         """Weight-compiled image: 0 = automatic (default), 64 = the 64-row
         image (one row per lane, VOP2 adds), 128 = the 128-row image."""
         _check(lib().tcsc_hip_set_tile_rows(self._h, rows), "tcsc_hip_set_tile_rows")
+
+    def last_launch(self):
+        """(workgroups, logical workgroup ids) of the handle's last
+        weight-compiled launch, as passed to the runtime (tcsc_hip_last_launch)."""
+        tiles = C.c_int()
+        return int(lib().tcsc_hip_last_launch(self._h, C.byref(tiles))), tiles.value
 
     def call_tile_rows(self, M: int) -> int:
         """M tile (64 / 128) of the weight-compiled image a call with M rows
