@@ -577,82 +577,73 @@ __global__ __launch_bounds__(kRxWaves * 64, 8 / kRxWaves) void tsg_tcsc_rx_kerne
 }
 
 // ---------------------------------------------------------------- launchers --
-// Calls f(std::integral_constant<int, Q>) with Q = what the staging pass does
-// to the values it loads (XStage, tsg_norm.h): quantise when inv is given,
-// normalise first when rn is given too.  An int8 X is never quantised (the
+// Calls launch(x, std::integral_constant<int, Q>) with x = X as its element
+// type and Q = what the staging pass does to the values it loads (XStage,
+// tsg_norm.h): quantise when inv is given, normalise first when rn is given
+// too; 0 when the launch went through.  An int8 X is never quantised (the
 // C-ABI refuses it), so those combinations are not instantiated.
-template <typename T, typename F>
-int with_quant(const float *inv, const float *rn, F &&f)
+template <typename F>
+int stage_launch(const XIn &in, F &&launch)
 {
-    if constexpr (std::is_same_v<T, xi8>) {
-        return inv ? -1 : f(std::integral_constant<int, kStageNone>{});
-    } else {
-        if (!inv) return f(std::integral_constant<int, kStageNone>{});
-        return rn ? f(std::integral_constant<int, kStageNorm>{}) : f(std::integral_constant<int, kStageQuant>{});
-    }
-}
-
-int launch_transpose(const void *X, int xtype, float *XT, int M, int K, int Mp, int Kp, void *stream,
-                     const float *inv, const float *rn, const float *g)
-{
-    dim3 grid((unsigned)((Kp + 63) / 64), (unsigned)(Mp / 64));
-    const bool vec = K % 4 == 0 && x_quad_aligned(X, xtype);
-    return with_xtype(X, xtype, [&](auto *x) {
-        using T = std::remove_cv_t<std::remove_pointer_t<decltype(x)>>;
-        return with_quant<T>(inv, rn, [&](auto q) {
-            constexpr int Q = decltype(q)::value;
-            if (vec)
-                hipLaunchKernelGGL((tsg_transpose4_kernel<T, Q>), grid, dim3(256), 0, (hipStream_t)stream, x, XT, M, K,
-                                   Mp, Kp, inv, rn, g);
-            else
-                hipLaunchKernelGGL((tsg_transpose_kernel<T, Q>), grid, dim3(256), 0, (hipStream_t)stream, x, XT, M, K,
-                                   Mp, Kp, inv, rn, g);
-            return hipGetLastError() == hipSuccess ? 0 : -1;
-        });
+    return with_xtype(in.X, in.xtype, [&](auto *x) {
+        auto go = [&](auto q) { return launch(x, q), hipGetLastError() == hipSuccess ? 0 : -1; };
+        if (!in.inv) return go(std::integral_constant<int, kStageNone>{});
+        if constexpr (std::is_same_v<decltype(x), const xi8 *>) return -1;
+        else return in.rn ? go(std::integral_constant<int, kStageNorm>{}) : go(std::integral_constant<int, kStageQuant>{});
     });
 }
 
+// whether a staging pass may load X a quad at a time
+static bool quad_loads(const XIn &in) { return in.K % 4 == 0 && x_quad_aligned(in.X, in.xtype); }
 
-int launch_transpose_pairs(const void *X, int xtype, float *XP, int M, int K, int Mp, int Kp, void *stream,
-                           const float *inv, const float *rn, const float *g)
+int launch_transpose(const XIn &in, float *XT, int Mp, int Kp, void *stream)
+{
+    dim3 grid((unsigned)((Kp + 63) / 64), (unsigned)(Mp / 64));
+    const bool vec = quad_loads(in);
+    return stage_launch(in, [&](auto *x, auto q) {
+        using T = std::remove_cv_t<std::remove_pointer_t<decltype(x)>>;
+        constexpr int Q = decltype(q)::value;
+        if (vec)
+            hipLaunchKernelGGL((tsg_transpose4_kernel<T, Q>), grid, dim3(256), 0, (hipStream_t)stream, x, XT, in.M, in.K,
+                               Mp, Kp, in.inv, in.rn, in.g);
+        else
+            hipLaunchKernelGGL((tsg_transpose_kernel<T, Q>), grid, dim3(256), 0, (hipStream_t)stream, x, XT, in.M, in.K,
+                               Mp, Kp, in.inv, in.rn, in.g);
+    });
+}
+
+int launch_transpose_pairs(const XIn &in, float *XP, int Mp, int Kp, void *stream)
 {
     // Mp is a multiple of 128 (the jit M tile) and Kp of 96: the 64 x 64 tiles
     // cover [0, Kp) x [0, Mp) exactly in m and up to 32 pad rows in k
     dim3 grid((unsigned)((Kp + 63) / 64), (unsigned)(Mp / 64));
-    const bool vec = K % 4 == 0 && x_quad_aligned(X, xtype);
-    return with_xtype(X, xtype, [&](auto *x) {
+    const bool vec = quad_loads(in);
+    return stage_launch(in, [&](auto *x, auto q) {
         using T = std::remove_cv_t<std::remove_pointer_t<decltype(x)>>;
-        return with_quant<T>(inv, rn, [&](auto q) {
-            constexpr int Q = decltype(q)::value;
-            if (vec)
-                hipLaunchKernelGGL((tsg_transpose_pairs_kernel<T, true, Q>), grid, dim3(256), 0, (hipStream_t)stream, x,
-                                   XP, M, K, Mp, Kp, inv, rn, g);
-            else
-                hipLaunchKernelGGL((tsg_transpose_pairs_kernel<T, false, Q>), grid, dim3(256), 0, (hipStream_t)stream,
-                                   x, XP, M, K, Mp, Kp, inv, rn, g);
-            return hipGetLastError() == hipSuccess ? 0 : -1;
-        });
+        constexpr int Q = decltype(q)::value;
+        if (vec)
+            hipLaunchKernelGGL((tsg_transpose_pairs_kernel<T, true, Q>), grid, dim3(256), 0, (hipStream_t)stream, x, XP,
+                               in.M, in.K, Mp, Kp, in.inv, in.rn, in.g);
+        else
+            hipLaunchKernelGGL((tsg_transpose_pairs_kernel<T, false, Q>), grid, dim3(256), 0, (hipStream_t)stream, x, XP,
+                               in.M, in.K, Mp, Kp, in.inv, in.rn, in.g);
     });
 }
 
-int launch_transpose_quads(const void *X, int xtype, float *XQ, int M, int K, int Mp, int Kp, int piece_rows,
-                           void *stream, int chunk, const float *inv, const float *rn, const float *g)
+int launch_transpose_quads(const XIn &in, float *XQ, int Mp, int Kp, int piece_rows, int chunk, void *stream)
 {
     hipStream_t s = (hipStream_t)stream;
-    const bool vec = K % 4 == 0 && x_quad_aligned(X, xtype);
+    const bool vec = quad_loads(in);
     if (piece_rows == 0) {  // the row layout: 188-row chunks, 47 KiB per (chunk, M tile)
         if (chunk != 188 || Mp % 64 || Kp % 188) return -1;
         const int nch = Kp / 188;
         const int64_t blocks = (int64_t)nch * (Mp / 64) * 4;
         if (blocks >= ((int64_t)1 << 31)) return -1;
-        return with_xtype(X, xtype, [&](auto *x) {
+        return stage_launch(in, [&](auto *x, auto q) {
             using T = std::remove_cv_t<std::remove_pointer_t<decltype(x)>>;
-            return with_quant<T>(inv, rn, [&](auto q) {
-                constexpr int Q = decltype(q)::value;
-                if (vec) hipLaunchKernelGGL((tsg_transpose_rows_kernel<T, true, Q>), dim3((unsigned)blocks), dim3(256), 0, s, x, XQ, M, K, Mp, nch, inv, rn, g);
-                else hipLaunchKernelGGL((tsg_transpose_rows_kernel<T, false, Q>), dim3((unsigned)blocks), dim3(256), 0, s, x, XQ, M, K, Mp, nch, inv, rn, g);
-                return hipGetLastError() == hipSuccess ? 0 : -1;
-            });
+            constexpr int Q = decltype(q)::value;
+            if (vec) hipLaunchKernelGGL((tsg_transpose_rows_kernel<T, true, Q>), dim3((unsigned)blocks), dim3(256), 0, s, x, XQ, in.M, in.K, Mp, nch, in.inv, in.rn, in.g);
+            else hipLaunchKernelGGL((tsg_transpose_rows_kernel<T, false, Q>), dim3((unsigned)blocks), dim3(256), 0, s, x, XQ, in.M, in.K, Mp, nch, in.inv, in.rn, in.g);
         });
     }
     // Mp is a multiple of 64 (the 64-row image's M tile) and Kp of 192 (its
@@ -664,43 +655,35 @@ int launch_transpose_quads(const void *X, int xtype, float *XQ, int M, int K, in
     if (blocks >= ((int64_t)1 << 31)) return -1;
     if (piece_rows != 16 && piece_rows != 8) return -1;
     dim3 grid((unsigned)blocks);
-    return with_xtype(X, xtype, [&](auto *x) {
+    return stage_launch(in, [&](auto *x, auto q) {
         using T = std::remove_cv_t<std::remove_pointer_t<decltype(x)>>;
-        return with_quant<T>(inv, rn, [&](auto q) {
-            constexpr int Q = decltype(q)::value;
-            if (piece_rows == 16) {
-                if (vec) hipLaunchKernelGGL((tsg_transpose_quads_kernel<T, true, 16, Q>), grid, dim3(256), 0, s, x, XQ, M, K, Mp, Kp, units, inv, rn, g);
-                else hipLaunchKernelGGL((tsg_transpose_quads_kernel<T, false, 16, Q>), grid, dim3(256), 0, s, x, XQ, M, K, Mp, Kp, units, inv, rn, g);
-            } else {
-                if (vec) hipLaunchKernelGGL((tsg_transpose_quads_kernel<T, true, 8, Q>), grid, dim3(256), 0, s, x, XQ, M, K, Mp, Kp, units, inv, rn, g);
-                else hipLaunchKernelGGL((tsg_transpose_quads_kernel<T, false, 8, Q>), grid, dim3(256), 0, s, x, XQ, M, K, Mp, Kp, units, inv, rn, g);
-            }
-            return hipGetLastError() == hipSuccess ? 0 : -1;
-        });
+        constexpr int Q = decltype(q)::value;
+        if (piece_rows == 16) {
+            if (vec) hipLaunchKernelGGL((tsg_transpose_quads_kernel<T, true, 16, Q>), grid, dim3(256), 0, s, x, XQ, in.M, in.K, Mp, Kp, units, in.inv, in.rn, in.g);
+            else hipLaunchKernelGGL((tsg_transpose_quads_kernel<T, false, 16, Q>), grid, dim3(256), 0, s, x, XQ, in.M, in.K, Mp, Kp, units, in.inv, in.rn, in.g);
+        } else {
+            if (vec) hipLaunchKernelGGL((tsg_transpose_quads_kernel<T, true, 8, Q>), grid, dim3(256), 0, s, x, XQ, in.M, in.K, Mp, Kp, units, in.inv, in.rn, in.g);
+            else hipLaunchKernelGGL((tsg_transpose_quads_kernel<T, false, 8, Q>), grid, dim3(256), 0, s, x, XQ, in.M, in.K, Mp, Kp, units, in.inv, in.rn, in.g);
+        }
     });
 }
 
-// The row pass of an actquant call: inv and deq (float[M] each) of every row,
-// deq also to out when given, and with q8 the int8 q of the whole X (the
-// small-M walks).  With rn (float[M]) the row pass of a normquant call: the
-// RMSNorm of tsg_norm.h with gamma g (may be null) and eps comes first, and
-// rn[m] is stored too.  An int8 X is refused (-1).
-int launch_row_absmax(const void *X, int xtype, int M, int K, float *inv, float *deq, float *out, int8_t *q8,
-                      void *stream, float *rn, const float *g, float eps)
+// (tsg_internal.h; an int8 X is refused: -1)
+int launch_row_absmax(const XIn &in, float *deq, float *out, int8_t *q8, float eps, void *stream)
 {
-    if (M <= 0) return 0;
-    if (xtype == kXI8) return -1;
+    if (in.M <= 0) return 0;
+    if (in.xtype == kXI8) return -1;
     hipStream_t s = (hipStream_t)stream;
-    const bool vec = K % 4 == 0 && x_quad_aligned(X, xtype);
-    const dim3 grid((unsigned)((M + 3) / 4));
-    return with_xtype(X, xtype, [&](auto *x) {
+    const bool vec = quad_loads(in);
+    const dim3 grid((unsigned)((in.M + 3) / 4));
+    return with_xtype(in.X, in.xtype, [&](auto *x) {
         using T = std::remove_cv_t<std::remove_pointer_t<decltype(x)>>;
         if constexpr (std::is_same_v<T, xi8>) {
             return -1;
         } else {
             auto go = [&](auto v, auto q, auto n) {
                 hipLaunchKernelGGL((tsg_row_absmax_kernel<T, decltype(v)::value, decltype(q)::value, decltype(n)::value>),
-                                   grid, dim3(256), 0, s, x, M, K, inv, deq, out, q8, rn, g, eps);
+                                   grid, dim3(256), 0, s, x, in.M, in.K, in.inv, deq, out, q8, in.rn, in.g, eps);
             };
             auto pick_q = [&](auto v, auto n) {
                 if (q8) go(v, std::true_type{}, n);
@@ -710,27 +693,23 @@ int launch_row_absmax(const void *X, int xtype, int M, int K, float *inv, float 
                 if (vec) pick_q(std::true_type{}, n);
                 else pick_q(std::false_type{}, n);
             };
-            if (rn) pick_v(std::true_type{});
+            if (in.rn) pick_v(std::true_type{});
             else pick_v(std::false_type{});
             return hipGetLastError() == hipSuccess ? 0 : -1;
         }
     });
 }
 
-int launch_tcsc_rx(const float *XT, int Mp, const uint32_t *wstart, const uint32_t *ent,
-                   const float *b, const float *alpha, const float *rs, const float *cs, const Epi &ep, void *Y,
-                   int ytype, int64_t ldY, int M, int N, int Npad, int nch, int prelu, void *stream)
+int launch_tcsc_rx(const float *XT, int Mp, const uint32_t *wstart, const uint32_t *ent, int Npad, int nch,
+                   const YOut &o)
 {
-    hipStream_t s = (hipStream_t)stream;
-    if (ep.on()) ytype |= kYEpi;  // the kernel's one test for a call with a fused epilogue (tsg_epilogue.h)
+    hipStream_t s = (hipStream_t)o.stream;
+    const int ytype = o.kernel_ytype(false);  // (the kernel tests the two scale pointers)
     const int mtiles = Mp / kRxTileM, ntiles = Npad / kRxTileCols;
     const dim3 grid((unsigned)(mtiles * ntiles)), block(kRxWaves * kLanes);
-    if (prelu)
-        hipLaunchKernelGGL((tsg_tcsc_rx_kernel<true>), grid, block, 0, s, XT, Mp, wstart, ent, b, alpha,
-                           static_cast<float *>(Y), ldY, ytype, M, N, nch, mtiles, ntiles, rs, cs, ep);
-    else
-        hipLaunchKernelGGL((tsg_tcsc_rx_kernel<false>), grid, block, 0, s, XT, Mp, wstart, ent, b, alpha,
-                           static_cast<float *>(Y), ldY, ytype, M, N, nch, mtiles, ntiles, rs, cs, ep);
+    auto *kernel = o.prelu ? tsg_tcsc_rx_kernel<true> : tsg_tcsc_rx_kernel<false>;
+    hipLaunchKernelGGL(kernel, grid, block, 0, s, XT, Mp, wstart, ent, o.b, o.alpha, static_cast<float *>(o.Y), o.ldY, ytype,
+                       o.M, o.N, nch, mtiles, ntiles, o.rs, o.cs, o.ep);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

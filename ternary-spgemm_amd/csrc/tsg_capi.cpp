@@ -435,31 +435,21 @@ int ensure_ell(tsg_tcsc *h, int v)
     return TSG_OK;
 }
 
-// One device-pointer call, as its launch functions see it
+// One device-pointer call: the two blocks its launchers take (tsg_internal.h)
+// and what only this file reads.  run_dev owns it.
 struct Call {
-    const void *dX;  // M x K row-major elements of xtype (tsg::XType)
-    int xtype;
-    const float *db, *dalpha;
-    const float *drs, *dcs;  // the epilogue scales, float[M] and float[N] (either may be null)
-    void *dY;     // elements of ytype (tsg::YType)
-    int ytype;
-    int64_t ldY;  // elements of ytype from one Y row to the next (>= N)
-    int M;
-    hipStream_t s;
-    bool prelu, capturing;
-    // an actquant call (tsg_actquant.h): X is quantised per row on the way in,
-    // drs is the scratch's deq (set by the launch functions), drs_out the
-    // caller's copy of it (may be null)
+    tsg::XIn in;    // X, xtype, M, K; g: the gamma of a normquant call (may be null)
+    tsg::YOut out;  // b, alpha, rs, cs, ep, Y, ytype, ldY, M, N, prelu, stream
+    bool capturing = false;
+    // an actquant call (tsg_actquant.h): X is quantised per row on the way in
+    // (stage_begin), drs_out is the caller's copy of deq (may be null)
     bool quant = false;
     float *drs_out = nullptr;
     // a normquant call (tsg_norm.h): an actquant call whose X goes through an
-    // RMSNorm with gamma dgamma (may be null) and eps first
+    // RMSNorm with gamma in.g and eps first
     bool norm = false;
-    const float *dgamma = nullptr;
     float eps = 0.0f;
-    // the fused epilogue of a tcsc_hip_gemm_dev_ex call (tsg_epilogue.h); none
-    // on every other call
-    tsg::Epi ep;
+    hipStream_t s() const { return (hipStream_t)out.stream; }
 };
 
 // Before a call stages its X^T: the work buffer holds it (ensure_work), and
@@ -467,12 +457,13 @@ struct Call {
 // stream: this call's staging waits for it (same stream: stream order)
 int work_begin(tsg_tcsc *h, const CallPlan &p, const Call &c)
 {
+    const int M = c.in.M;
     // (a walk has no X^T: it comes here for the actquant scratch alone)
-    int rc = p.is_ell() ? TSG_OK : ensure_work(h, c.M, p.tile_m, p.chunk, c.capturing);
+    int rc = p.is_ell() ? TSG_OK : ensure_work(h, M, p.tile_m, p.chunk, c.capturing);
     if (!rc && c.quant)
-        rc = ensure_aq(h, c.M, p.is_ell() ? std::max<size_t>((size_t)c.M * h->plan.K, 16) : 0, c.capturing);
+        rc = ensure_aq(h, M, p.is_ell() ? std::max<size_t>((size_t)M * h->plan.K, 16) : 0, c.capturing);
     if (rc) return rc;
-    if (!c.capturing && h->work_used && h->work_stream != c.s) HIP_TRY(hipStreamWaitEvent(c.s, h->work_ev, 0));
+    if (!c.capturing && h->work_used && h->work_stream != c.s()) HIP_TRY(hipStreamWaitEvent(c.s(), h->work_ev, 0));
     return TSG_OK;
 }
 
@@ -485,112 +476,110 @@ int work_begin(tsg_tcsc *h, const CallPlan &p, const Call &c)
 int work_end(tsg_tcsc *h, const Call &c)
 {
     if (c.capturing) return TSG_OK;
-    HIP_TRY(hipEventRecord(h->work_ev, c.s));
-    h->work_stream = c.s;
+    HIP_TRY(hipEventRecord(h->work_ev, c.s()));
+    h->work_stream = c.s();
     h->work_used = true;
     return TSG_OK;
 }
 
-// The row pass of an actquant call, after work_begin: inv and deq of every row
-// into the scratch (and deq to the caller), for a walk also the int8 q; of a
-// normquant call also rn, and everything is taken of the normalised row
-int quant_rows(tsg_tcsc *h, const Call &c, bool q8)
+// work_begin, then for an actquant call the row pass: the call's blocks take
+// the scratch (tsg_tcsc::d_aq: inv and, of a normquant call, rn for the pass
+// that reads X, deq as the row scale of the kernel that stores Y) and the pass
+// fills them (deq also to the caller), for a walk (q8) also the int8 q
+int stage_begin(tsg_tcsc *h, const CallPlan &p, Call &c, bool q8)
 {
-    if (tsg::launch_row_absmax(c.dX, c.xtype, c.M, h->plan.K, h->d_aq, h->d_aq + h->aq_rows, c.drs_out,
-                               q8 ? h->d_aq8 : nullptr, c.s, c.norm ? h->d_aq + 2 * h->aq_rows : nullptr, c.dgamma,
-                               c.eps) != 0)
+    const int rc = work_begin(h, p, c);
+    if (rc || !c.quant) return rc;
+    float *const deq = h->d_aq + h->aq_rows;
+    c.in.inv = h->d_aq;
+    c.in.rn = c.norm ? h->d_aq + 2 * h->aq_rows : nullptr;
+    c.out.rs = deq;
+    if (tsg::launch_row_absmax(c.in, deq, c.drs_out, q8 ? h->d_aq8 : nullptr, c.eps, c.s()) != 0)
         return fail(TSG_ERR_HIP, std::string("row pass launch: ") + hipGetErrorString(hipGetLastError()));
     return TSG_OK;
 }
 
 // small M: the ELL walk reads X in place, whatever its element type (no X^T
 // staging, no work buffer)
-int run_ell(tsg_tcsc *h, const CallPlan &p, const Call &c0)
+int run_ell(tsg_tcsc *h, const CallPlan &p, Call &c)
 {
-    if (!h->ell[p.ell].ready && c0.capturing)
-        return fail(TSG_ERR_ARG, "M=" + std::to_string(c0.M) + " runs the small-M kernel, whose image is not "
+    if (!h->ell[p.ell].ready && c.capturing)
+        return fail(TSG_ERR_ARG, "M=" + std::to_string(c.in.M) + " runs the small-M kernel, whose image is not "
                                  "built yet; call tcsc_hip_reserve before capturing");
     int rc = ensure_ell(h, p.ell);
     if (rc) return rc;
     // an actquant call: the row pass writes q as int8 into the scratch, and the
     // walk runs on it as an int8-X call scaled by the scratch's deq
-    Call c = c0;
     if (c.quant) {
-        rc = work_begin(h, p, c);
-        if (!rc) rc = quant_rows(h, c, true);
+        rc = stage_begin(h, p, c, true);
         if (rc) return rc;
-        c.dX = h->d_aq8;
-        c.xtype = tsg::kXI8;
-        c.drs = h->d_aq + h->aq_rows;
+        c.in.X = h->d_aq8, c.in.xtype = tsg::kXI8;
     }
     int slot;
-    rc = timing_begin(h, c.capturing, c.s, slot);
+    rc = timing_begin(h, c.capturing, c.s(), slot);
     if (rc) return rc;
-    const tsg_tcsc::EllVariant &e = h->ell[p.ell];
-    const int N = h->plan.N, K = h->plan.K;
-    const int lrc = p.kernel == Kernel::kEllPc
-                        ? tsg::launch_tcsc_ell_pc(p.ell, c.dX, c.xtype, e.d_ent, e.d_tab, c.db, c.dalpha, c.drs, c.dcs, c.ep, c.dY, c.ytype,
-                                                  c.ldY,                                                  c.M, N, K, e.img.C, e.img.nch, c.prelu ? 1 : 0, c.s)
-                        : tsg::launch_tcsc_ell(p.ell, c.dX, c.xtype, e.d_ent, e.d_tab, c.db, c.dalpha, c.drs, c.dcs, c.ep, c.dY, c.ytype, c.ldY,
-                                               c.M,                                               N, K, e.img.C, e.img.nch, e.img.xb, e.img.zr, c.prelu ? 1 : 0, c.s);
+    const tsg_tcsc::EllVariant &v = h->ell[p.ell];
+    tsg::EllDev e;
+    e.ent = v.d_ent, e.tab = v.d_tab, e.K = h->plan.K;
+    e.C = v.img.C, e.nch = v.img.nch, e.xb = v.img.xb, e.zr = v.img.zr;
+    const int lrc = p.kernel == Kernel::kEllPc ? tsg::launch_tcsc_ell_pc(p.ell, c.in.X, c.in.xtype, e, c.out)
+                                               : tsg::launch_tcsc_ell(p.ell, c.in.X, c.in.xtype, e, c.out);
     if (lrc != 0)
         return fail(TSG_ERR_HIP, std::string("small-M kernel launch: ") + hipGetErrorString(hipGetLastError()));
-    rc = timing_end(h, slot, c.s);
+    rc = timing_end(h, slot, c.s());
     return rc || !c.quant ? rc : work_end(h, c);
 }
 
 // the register-X walk: X^T pass, then the kernel
-int run_rx(tsg_tcsc *h, const CallPlan &p, const Call &c)
+int run_rx(tsg_tcsc *h, const CallPlan &p, Call &c)
 {
-    const int N = h->plan.N, K = h->plan.K;
-    const XtDims d = dims_for(c.M, K, p.tile_m, p.chunk);
-    int rc = work_begin(h, p, c);
-    if (!rc && c.quant) rc = quant_rows(h, c, false);
+    const int K = h->plan.K;
+    const XtDims d = dims_for(c.in.M, K, p.tile_m, p.chunk);
+    int rc = stage_begin(h, p, c, false);
     if (rc) return rc;
-    const float *inv = c.quant ? h->d_aq : nullptr;
-    const float *drs = c.quant ? h->d_aq + h->aq_rows : c.drs;
-    const float *rn = c.norm ? h->d_aq + 2 * h->aq_rows : nullptr;
     if (K == 0) {
         // no X at all: chain is +0; X^T stays zero
-        HIP_TRY(hipMemsetAsync(h->d_work, 0, (size_t)d.Mp * d.Kp * sizeof(float), c.s));
-    } else if (tsg::launch_transpose(c.dX, c.xtype, h->d_work, c.M, K, d.Mp, d.Kp, c.s, inv, rn, c.dgamma) != 0) {
+        HIP_TRY(hipMemsetAsync(h->d_work, 0, (size_t)d.Mp * d.Kp * sizeof(float), c.s()));
+    } else if (tsg::launch_transpose(c.in, h->d_work, d.Mp, d.Kp, c.s()) != 0) {
         return fail(TSG_ERR_HIP, std::string("transpose launch: ") + hipGetErrorString(hipGetLastError()));
     }
     int slot;
-    rc = timing_begin(h, c.capturing, c.s, slot);
+    rc = timing_begin(h, c.capturing, c.s(), slot);
     if (rc) return rc;
-    if (tsg::launch_tcsc_rx(h->d_work, d.Mp, h->d_seg, h->d_ent, c.db, c.dalpha, drs, c.dcs, c.ep, c.dY, c.ytype, c.ldY, c.M, N,
-                            h->rimg.Npad, h->rimg.nch, c.prelu ? 1 : 0, c.s) != 0)
+    if (tsg::launch_tcsc_rx(h->d_work, d.Mp, h->d_seg, h->d_ent, h->rimg.Npad, h->rimg.nch, c.out) != 0)
         return fail(TSG_ERR_HIP, std::string("tcsc launch: ") + hipGetErrorString(hipGetLastError()));
-    rc = timing_end(h, slot, c.s);
+    rc = timing_end(h, slot, c.s());
     return rc ? rc : work_end(h, c);
 }
 
 // a weight-compiled image `jv` (loaded): X^T pass unless the image reads X
 // itself, then the dispatcher
-int run_jit(tsg_tcsc *h, const CallPlan &p, const tsg_tcsc::JitVariant &jv, const Call &c)
+int run_jit(tsg_tcsc *h, const CallPlan &p, const tsg_tcsc::JitVariant &jv, Call &c)
 {
-    const int N = h->plan.N, K = h->plan.K;
+    const int M = c.in.M, N = h->plan.N, K = h->plan.K;
     const bool r64 = p.kernel == Kernel::kJit64;
-    const XtDims d = dims_for(c.M, K, p.tile_m, p.chunk);
+    const XtDims d = dims_for(M, K, p.tile_m, p.chunk);
+    tsg::JitLaunch g;  // of the call, the image and the plan
+    g.Mp = d.Mp, g.status = h->d_status;
+    g.wcode = jv.d_wcode, g.Npad = jv.Npad, g.nch = jv.nch, g.tile_cols = jv.nw * jv.waves;
+    g.waves = jv.pair ? 2 * jv.waves : jv.waves;  // waves launched per workgroup
+    g.gn = p.gn, g.gm = p.gm, g.tmask = p.tmask, g.tile_m = p.tile_m, g.xtouch = p.xtouch, g.tnear = p.tnear;
     // the stream steps through X^T chunks with a 32-bit stride, and the grid
     // (one workgroup per M tile x column tile) must stay under 2^32 threads
-    const int waves = jv.pair ? 2 * jv.waves : jv.waves;  // waves launched per workgroup
     // (waves: the pair factor included; the logical ids are 32-bit in the kernel)
     // (= Mp / tile_m x Npad / cols, what launch_tcsc_jit derives for the kernel)
-    const int64_t wgs = tsg::jit_tiles(c.M, N, p.tile_m, jv.nw * jv.waves);
-    if ((int64_t)d.Mp * p.chunk * 4 >= (1ll << 31) || wgs * waves * 64 >= (1ll << 32) || wgs >= (1ll << 31))
-        return fail(TSG_ERR_ARG, "M=" + std::to_string(c.M) + " is too large for one jit launch; split the rows");
+    const int64_t wgs = tsg::jit_tiles(M, N, p.tile_m, g.tile_cols);
+    if ((int64_t)d.Mp * p.chunk * 4 >= (1ll << 31) || wgs * g.waves * 64 >= (1ll << 32) || wgs >= (1ll << 31))
+        return fail(TSG_ERR_ARG, "M=" + std::to_string(M) + " is too large for one jit launch; split the rows");
     // the looping launch (TSG_JIT_LOOP; tsg_plan.cpp loop_wgs): that many
     // workgroups, each running every loop-th logical id
-    int loop = jv.pair ? 0 : tsg::loop_wgs(p.shape, wgs);
-    int lflags = 0;
+    g.loop_wgs = jv.pair ? 0 : tsg::loop_wgs(p.shape, wgs);
 #ifdef TSG_DIAG
     if (const char *dv = tsg::knob_value("TSG_JIT_DIAG")) {  // results WRONG (timing studies)
-        if (std::strstr(dv, "nostore")) lflags |= tsg::kJitDiagNoStore;
+        if (std::strstr(dv, "nostore")) g.lflags |= tsg::kJitDiagNoStore;
         if (std::strstr(dv, "onetile")) {  // the first round alone
-            lflags |= tsg::kJitDiagOneTile;
-            loop = (int)std::min<int64_t>(wgs, std::max(h->cus / 8 * 8, 8));
+            g.lflags |= tsg::kJitDiagOneTile;
+            g.loop_wgs = (int)std::min<int64_t>(wgs, std::max(h->cus / 8 * 8, 8));
         }
     }
 #endif
@@ -600,87 +589,91 @@ int run_jit(tsg_tcsc *h, const CallPlan &p, const tsg_tcsc::JitVariant &jv, cons
     // the pass that widens it -- also at shapes where an fp32 X needs no work
     // buffer, which tcsc_hip_reserve sizes for the staged copy regardless)
     // (an actquant call is staged too: its staging pass quantises)
-    const bool direct = !c.quant && c.xtype == tsg::kXF32 &&
-                        tsg::x_direct(h->plan, p.shape, jv.piece_rows, ((uintptr_t)c.dX & 15) == 0, c.M);
+    const bool direct = !c.quant && c.in.xtype == tsg::kXF32 &&
+                        tsg::x_direct(h->plan, p.shape, jv.piece_rows, ((uintptr_t)c.in.X & 15) == 0, M);
     if (r64 && jv.chunk != p.chunk)  // the image and this call's X^T dims must agree (TSG_JIT_QBLOCK read at both)
         return fail(TSG_ERR_ARG, "64-row image built for " + std::to_string(jv.chunk) + "-row chunks, call expects " +
                                      std::to_string(p.chunk) + " (TSG_JIT_QBLOCK changed after the image was built)");
-    // row layout, direct X: the last chunk starts at K - 188, lastadj bytes
-    // below its slot (tsg_internal.h jit64_row_kbase)
-    const int lastadj = direct && jv.piece_rows == 0
-                            ? 4 * ((jv.nch - 1) * tsg::kJit64RowChunk - tsg::jit64_row_kbase(K, jv.nch, jv.nch - 1))
-                            : 0;
     int rc;
-    const float *inv = nullptr, *drs = c.drs, *rn = nullptr;
-    if (!direct) {  // (direct: no staging kernel, the dispatcher's DMA reads X itself)
-        rc = work_begin(h, p, c);
-        if (!rc && c.quant) rc = quant_rows(h, c, false);
+    if (direct) {  // no staging kernel: the dispatcher's DMA reads X (fp32) itself
+        g.xrow = K;
+        // row layout: the last chunk starts at K - 188, lastadj bytes below its
+        // slot (tsg_internal.h jit64_row_kbase)
+        if (jv.piece_rows == 0)
+            g.lastadj = 4 * ((jv.nch - 1) * tsg::kJit64RowChunk - tsg::jit64_row_kbase(K, jv.nch, jv.nch - 1));
+    } else {
+        rc = stage_begin(h, p, c, false);
         if (rc) return rc;
-        if (c.quant) {
-            inv = h->d_aq;
-            drs = h->d_aq + h->aq_rows;
-            if (c.norm) rn = h->d_aq + 2 * h->aq_rows;
-        }
         if (K == 0) {
             // no X at all: chain is +0; X^T stays zero
-            HIP_TRY(hipMemsetAsync(h->d_work, 0, (size_t)d.Mp * d.Kp * sizeof(float), c.s));
-        } else if ((r64 ? tsg::launch_transpose_quads(c.dX, c.xtype, h->d_work, c.M, K, d.Mp, d.Kp, jv.piece_rows, c.s,
-                                                      p.chunk, inv, rn, c.dgamma)
-                        : tsg::launch_transpose_pairs(c.dX, c.xtype, h->d_work, c.M, K, d.Mp, d.Kp, c.s, inv, rn,
-                                                      c.dgamma)) != 0) {
+            HIP_TRY(hipMemsetAsync(h->d_work, 0, (size_t)d.Mp * d.Kp * sizeof(float), c.s()));
+        } else if ((r64 ? tsg::launch_transpose_quads(c.in, h->d_work, d.Mp, d.Kp, jv.piece_rows, p.chunk, c.s())
+                        : tsg::launch_transpose_pairs(c.in, h->d_work, d.Mp, d.Kp, c.s())) != 0) {
             return fail(TSG_ERR_HIP, std::string("transpose launch: ") + hipGetErrorString(hipGetLastError()));
         }
     }
     int slot;
-    rc = timing_begin(h, c.capturing, c.s, slot);
+    rc = timing_begin(h, c.capturing, c.s(), slot);
     if (rc) return rc;
     int launched[2] = {0, 0};
-    if (tsg::launch_tcsc_jit(jv.mod, direct ? static_cast<const float *>(c.dX) : h->d_work, d.Mp, jv.d_wcode, c.db,
-                             c.dalpha, drs, c.dcs, c.ep, c.dY, c.ytype, c.ldY, c.M, N,
-                             jv.Npad, jv.nch, c.prelu ? 1 : 0, h->d_status, jv.nw * jv.waves, waves, p.gn, p.gm, p.tmask,
-                             c.s, p.tile_m, direct ? K : 0, lastadj, p.xtouch, p.tnear, loop, lflags, launched) != 0)
+    // (the work buffer as stage_begin left it: it may have grown)
+    if (tsg::launch_tcsc_jit(jv.mod, direct ? c.in.X : h->d_work, g, c.out, launched) != 0)
         return fail(TSG_ERR_HIP, std::string("tcsc launch: ") + hipGetErrorString(hipGetLastError()));
     h->last_grid = launched[0];
     h->last_tiles = launched[1];
-    rc = timing_end(h, slot, c.s);
+    rc = timing_end(h, slot, c.s());
     if (rc || direct) return rc;
     return work_end(h, c);
 }
 
-int run_dev(tsg_tcsc *h, const void *dX, const float *db, const float *dalpha, void *dY, int64_t ldY, int M,
-            int N, int K, hipStream_t s, bool prelu, int xtype = tsg::kXF32, int ytype = tsg::kYF32,
-            const float *drs = nullptr, const float *dcs = nullptr, bool quant = false, float *drs_out = nullptr,
-            bool norm = false, const float *dgamma = nullptr, float eps = 0.0f, const tsg::Epi &ep = tsg::Epi())
+int check_shape(const tsg_tcsc *h, int N, int K)
 {
+    if (N == h->plan.N && K == h->plan.K) return TSG_OK;
+    return fail(TSG_ERR_ARG, "shape mismatch: handle has K=" + std::to_string(h->plan.K) + " N=" +
+                                 std::to_string(h->plan.N) + ", call has K=" + std::to_string(K) +
+                                 " N=" + std::to_string(N));
+}
+
+// What every device-pointer call refuses before anything is enqueued, in the
+// order that decides which of two faults a call reports
+int check_call(const tsg_tcsc *h, const Call &c)
+{
+    const tsg::XIn &in = c.in;
+    const tsg::YOut &o = c.out;
     if (!h) return fail(TSG_ERR_ARG, "null handle");
-    if (norm && !(std::isfinite(eps) && eps > 0.0f))  // refused before anything is enqueued
-        return fail(TSG_ERR_ARG, "eps=" + std::to_string(eps) + ": the normquant calls need a finite eps > 0");
-    if (quant && xtype == tsg::kXI8)  // refused before anything is enqueued
+    if (c.norm && !(std::isfinite(c.eps) && c.eps > 0.0f))
+        return fail(TSG_ERR_ARG, "eps=" + std::to_string(c.eps) + ": the normquant calls need a finite eps > 0");
+    if (c.quant && in.xtype == tsg::kXI8)
         return fail(TSG_ERR_ARG, "xtype=3 (int8): the actquant and normquant calls quantise an fp32, fp16 or bf16 X; an int8 X "
                                  "goes to tcsc_hip_gemm_dev_scaled with its own scale");
-    if (!tsg::xtype_ok(xtype))  // refused before anything is enqueued
+    if (!tsg::xtype_ok(in.xtype))
         return fail(TSG_ERR_ARG,
-                    "xtype=" + std::to_string(xtype) + " is not a tsg_xtype (0 fp32, 1 fp16, 2 bf16, 3 int8)");
-    if (!tsg::ytype_ok(ytype))  // likewise
-        return fail(TSG_ERR_ARG, "ytype=" + std::to_string(ytype) + " is not a tsg_ytype (0 fp32, 1 fp16, 2 bf16)");
-    if (N != h->plan.N || K != h->plan.K)
-        return fail(TSG_ERR_ARG, "shape mismatch: handle has K=" + std::to_string(h->plan.K) + " N=" +
-                                     std::to_string(h->plan.N) + ", call has K=" + std::to_string(K) +
-                                     " N=" + std::to_string(N));
-    if (M < 0) return fail(TSG_ERR_ARG, "M < 0");
-    if (ldY < N)  // rows would overlap: refused before anything is enqueued
-        return fail(TSG_ERR_ARG, "ldY=" + std::to_string(ldY) + " is less than N=" + std::to_string(N));
-    if (M == 0 || N == 0) return TSG_OK;
-    if (!dY || !db || (K > 0 && !dX) || (prelu && !dalpha))
+                    "xtype=" + std::to_string(in.xtype) + " is not a tsg_xtype (0 fp32, 1 fp16, 2 bf16, 3 int8)");
+    if (!tsg::ytype_ok(o.ytype))
+        return fail(TSG_ERR_ARG, "ytype=" + std::to_string(o.ytype) + " is not a tsg_ytype (0 fp32, 1 fp16, 2 bf16)");
+    const int rc = check_shape(h, o.N, in.K);
+    if (rc) return rc;
+    if (o.M < 0) return fail(TSG_ERR_ARG, "M < 0");
+    if (o.ldY < o.N)  // rows would overlap
+        return fail(TSG_ERR_ARG, "ldY=" + std::to_string(o.ldY) + " is less than N=" + std::to_string(o.N));
+    if (o.M == 0 || o.N == 0) return TSG_OK;  // an empty call reads no pointer
+    if (!o.Y || !o.b || (in.K > 0 && !in.X) || (o.prelu && !o.alpha))
         return fail(TSG_ERR_ARG, "null device pointer");
+    return TSG_OK;
+}
+
+int run_dev(tsg_tcsc *h, Call c)
+{
+    const int rc0 = check_call(h, c);
+    if (rc0 || c.out.M == 0 || c.out.N == 0) return rc0;
+    const int M = c.in.M;
     DeviceGuard g(h->device);
     // One call at a time per handle: the X^T work buffer, the jit images and
     // the timing ring are shared by every stream that uses the handle.
     std::lock_guard<std::mutex> lk(h->mu);
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    HIP_TRY(hipStreamIsCapturing(s, &cap));
-    const Call c{dX, xtype, db, dalpha, drs, dcs, dY, ytype, ldY, M, s, prelu, cap != hipStreamCaptureStatusNone,
-                 quant, drs_out, norm, dgamma, eps, ep};
+    HIP_TRY(hipStreamIsCapturing(c.s(), &cap));
+    c.capturing = cap != hipStreamCaptureStatusNone;
     CallPlan p = tsg::plan_call(h->plan, M);
     if (p.is_ell()) return run_ell(h, p, c);
     if (!p.is_jit()) return run_rx(h, p, c);
@@ -688,10 +681,38 @@ int run_dev(tsg_tcsc *h, const void *dX, const float *db, const float *dalpha, v
         if (c.capturing)
             return fail(TSG_ERR_ARG, "M=" + std::to_string(M) + " runs the width-" + std::to_string(p.shape.nw) +
                                          " image, which is not compiled yet; call tcsc_hip_reserve before capturing");
-        const int rc = ensure_call_image(h, M, p, s);
+        const int rc = ensure_call_image(h, M, p, c.s());
         if (rc) return rc;
     }
     return run_jit(h, p, variant_of(h, p.shape), c);
+}
+
+// The fields every device-pointer call has, in the order of the C signatures
+Call dev_call(const void *dX, int xtype, const float *db, void *dY, int ytype, int64_t ldY, int M, int N, int K,
+              void *stream)
+{
+    Call c;
+    c.in.X = dX, c.in.xtype = xtype, c.in.M = M, c.in.K = K;
+    c.out.b = db, c.out.Y = dY, c.out.ytype = ytype, c.out.ldY = ldY, c.out.M = M, c.out.N = N;
+    c.out.stream = stream;
+    return c;
+}
+
+// ... and what a _prelu, an _actquant and a _normquant call add
+Call with_prelu(Call c, const float *dalpha)
+{
+    c.out.alpha = dalpha, c.out.prelu = true;
+    return c;
+}
+Call with_quant(Call c, float *drow_scale_out, const float *dcol_scale)
+{
+    c.quant = true, c.drs_out = drow_scale_out, c.out.cs = dcol_scale;
+    return c;
+}
+Call with_norm(Call c, const float *dgamma, float eps)
+{
+    c.norm = true, c.in.g = dgamma, c.eps = eps;
+    return c;
 }
 
 int host_pipe_ready(tsg_tcsc *h)
@@ -734,8 +755,7 @@ int run_host_impl(tsg_tcsc *h, const float *X, const float *b, const float *alph
                   bool prelu)
 {
     if (!h) return fail(TSG_ERR_ARG, "null handle");
-    if (N != h->plan.N || K != h->plan.K)
-        return run_dev(h, nullptr, nullptr, nullptr, nullptr, N, M, N, K, nullptr, prelu);
+    if (const int rc = check_shape(h, N, K)) return rc;
     if (M < 0) return fail(TSG_ERR_ARG, "M < 0");
     if (M == 0 || N == 0) return TSG_OK;
     if (!Y || !b || (K > 0 && !X) || (prelu && !alpha)) return fail(TSG_ERR_ARG, "null host pointer");
@@ -763,10 +783,15 @@ int run_host_impl(tsg_tcsc *h, const float *X, const float *b, const float *alph
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(h->d_b, b, (size_t)N * sizeof(float), hipMemcpyHostToDevice, s));
     if (prelu) HIP_TRY(hipMemcpyAsync(h->d_alpha, alpha, (size_t)N * sizeof(float), hipMemcpyHostToDevice, s));
+    auto run_rows = [&](size_t r0, size_t nr) {  // the device call of rows [r0, r0 + nr) of the staged X
+        Call c = dev_call(h->d_x + r0 * K, tsg::kXF32, h->d_b, h->d_y + r0 * N, tsg::kYF32, N, (int)nr, N, K, s);
+        c.out.alpha = h->d_alpha, c.out.prelu = prelu;
+        return run_dev(h, c);
+    };
     const int rows = tsg::host_chunk_rows(h->plan, h->host_chunks, M);
     if (rows >= M) {
         if (xb) HIP_TRY(hipMemcpyAsync(h->d_x, X, xb, hipMemcpyHostToDevice, s));
-        rc = run_dev(h, h->d_x, h->d_b, h->d_alpha, h->d_y, N, M, N, K, s, prelu);
+        rc = run_rows(0, (size_t)M);
         if (rc) return rc;
         HIP_TRY(hipMemcpyAsync(Y, h->d_y, yb, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
@@ -834,7 +859,7 @@ int run_host_impl(tsg_tcsc *h, const float *X, const float *b, const float *alph
         if (e == hipSuccess) e = hipEventRecord(h->ev_in[i], h->s_in);
         if (e == hipSuccess) e = hipStreamWaitEvent(s, h->ev_in[i], 0);
         if (e != hipSuccess) return stop(fail(TSG_ERR_HIP, std::string("host pipeline (X chunk): ") + hipGetErrorString(e)));
-        rc = run_dev(h, h->d_x + r0 * K, h->d_b, h->d_alpha, h->d_y + r0 * N, N, (int)nr, N, K, s, prelu);
+        rc = run_rows(r0, nr);
         if (rc) return stop(rc);
         e = hipEventRecord(h->ev_c[i], s);
         if (e != hipSuccess) return stop(fail(TSG_ERR_HIP, std::string("host pipeline (event): ") + hipGetErrorString(e)));
@@ -1441,76 +1466,78 @@ extern "C" int tcsc_hip_gemm_prelu(tsg_tcsc *h, const float *X, const float *b, 
 extern "C" int tcsc_hip_gemm_dev(tsg_tcsc *h, const float *dX, const float *db, float *dY, int M,
                                  int N, int K, void *stream)
 {
-    return run_dev(h, dX, db, nullptr, dY, N, M, N, K, (hipStream_t)stream, false);
+    return run_dev(h, dev_call(dX, tsg::kXF32, db, dY, tsg::kYF32, N, M, N, K, stream));
 }
 
 extern "C" int tcsc_hip_gemm_prelu_dev(tsg_tcsc *h, const float *dX, const float *db,
                                        const float *dalpha, float *dY, int M, int N, int K,
                                        void *stream)
 {
-    return run_dev(h, dX, db, dalpha, dY, N, M, N, K, (hipStream_t)stream, true);
+    return run_dev(h, with_prelu(dev_call(dX, tsg::kXF32, db, dY, tsg::kYF32, N, M, N, K, stream), dalpha));
 }
 
 extern "C" int tcsc_hip_gemm_dev_ld(tsg_tcsc *h, const float *dX, const float *db, float *dY, int64_t ldY,
                                     int M, int N, int K, void *stream)
 {
-    return run_dev(h, dX, db, nullptr, dY, ldY, M, N, K, (hipStream_t)stream, false);
+    return run_dev(h, dev_call(dX, tsg::kXF32, db, dY, tsg::kYF32, ldY, M, N, K, stream));
 }
 
 extern "C" int tcsc_hip_gemm_prelu_dev_ld(tsg_tcsc *h, const float *dX, const float *db, const float *dalpha,
                                           float *dY, int64_t ldY, int M, int N, int K, void *stream)
 {
-    return run_dev(h, dX, db, dalpha, dY, ldY, M, N, K, (hipStream_t)stream, true);
+    return run_dev(h, with_prelu(dev_call(dX, tsg::kXF32, db, dY, tsg::kYF32, ldY, M, N, K, stream), dalpha));
 }
 
 // X of another element type (tsg_xtype): the same calls, the type carried to
-// the pass that reads X (Call::xtype); TSG_X_F32 is tcsc_hip_gemm_dev_ld
+// the pass that reads X (XIn::xtype); TSG_X_F32 is tcsc_hip_gemm_dev_ld
 extern "C" int tcsc_hip_gemm_dev_x(tsg_tcsc *h, const void *dX, int xtype, const float *db, float *dY, int64_t ldY,
                                    int M, int N, int K, void *stream)
 {
-    return run_dev(h, dX, db, nullptr, dY, ldY, M, N, K, (hipStream_t)stream, false, xtype);
+    return run_dev(h, dev_call(dX, xtype, db, dY, tsg::kYF32, ldY, M, N, K, stream));
 }
 
 extern "C" int tcsc_hip_gemm_prelu_dev_x(tsg_tcsc *h, const void *dX, int xtype, const float *db,
                                          const float *dalpha, float *dY, int64_t ldY, int M, int N, int K,
                                          void *stream)
 {
-    return run_dev(h, dX, db, dalpha, dY, ldY, M, N, K, (hipStream_t)stream, true, xtype);
+    return run_dev(h, with_prelu(dev_call(dX, xtype, db, dY, tsg::kYF32, ldY, M, N, K, stream), dalpha));
 }
 
 // Y of another element type (tsg_ytype): the same calls again, the type carried
-// to the epilogue of the kernel that stores Y (Call::ytype); TSG_Y_F32 is
+// to the epilogue of the kernel that stores Y (YOut::ytype); TSG_Y_F32 is
 // tcsc_hip_gemm_dev_x
 extern "C" int tcsc_hip_gemm_dev_xy(tsg_tcsc *h, const void *dX, int xtype, const float *db, void *dY, int ytype,
                                     int64_t ldY, int M, int N, int K, void *stream)
 {
-    return run_dev(h, dX, db, nullptr, dY, ldY, M, N, K, (hipStream_t)stream, false, xtype, ytype);
+    return run_dev(h, dev_call(dX, xtype, db, dY, ytype, ldY, M, N, K, stream));
 }
 
 extern "C" int tcsc_hip_gemm_prelu_dev_xy(tsg_tcsc *h, const void *dX, int xtype, const float *db,
                                           const float *dalpha, void *dY, int ytype, int64_t ldY, int M, int N, int K,
                                           void *stream)
 {
-    return run_dev(h, dX, db, dalpha, dY, ldY, M, N, K, (hipStream_t)stream, true, xtype, ytype);
+    return run_dev(h, with_prelu(dev_call(dX, xtype, db, dY, ytype, ldY, M, N, K, stream), dalpha));
 }
 
 // The epilogue scales (tsg_scale.h): the _xy calls again with a per-row and a
-// per-column scale between the chain and + b[n] (Call::drs, Call::dcs); with
+// per-column scale between the chain and + b[n] (YOut::rs, YOut::cs); with
 // both null they are the _xy calls
 extern "C" int tcsc_hip_gemm_dev_scaled(tsg_tcsc *h, const void *dX, int xtype, const float *drow_scale,
                                         const float *dcol_scale, const float *db, void *dY, int ytype, int64_t ldY,
                                         int M, int N, int K, void *stream)
 {
-    return run_dev(h, dX, db, nullptr, dY, ldY, M, N, K, (hipStream_t)stream, false, xtype, ytype, drow_scale,
-                   dcol_scale);
+    Call c = dev_call(dX, xtype, db, dY, ytype, ldY, M, N, K, stream);
+    c.out.rs = drow_scale, c.out.cs = dcol_scale;
+    return run_dev(h, c);
 }
 
 extern "C" int tcsc_hip_gemm_prelu_dev_scaled(tsg_tcsc *h, const void *dX, int xtype, const float *drow_scale,
                                               const float *dcol_scale, const float *db, const float *dalpha, void *dY,
                                               int ytype, int64_t ldY, int M, int N, int K, void *stream)
 {
-    return run_dev(h, dX, db, dalpha, dY, ldY, M, N, K, (hipStream_t)stream, true, xtype, ytype, drow_scale,
-                   dcol_scale);
+    Call c = with_prelu(dev_call(dX, xtype, db, dY, ytype, ldY, M, N, K, stream), dalpha);
+    c.out.rs = drow_scale, c.out.cs = dcol_scale;
+    return run_dev(h, c);
 }
 
 // Fused per-row int8 activation quantisation (tsg_actquant.h): the _scaled
@@ -1520,28 +1547,27 @@ extern "C" int tcsc_hip_gemm_dev_actquant(tsg_tcsc *h, const void *dX, int xtype
                                           const float *dcol_scale, const float *db, void *dY, int ytype, int64_t ldY,
                                           int M, int N, int K, void *stream)
 {
-    return run_dev(h, dX, db, nullptr, dY, ldY, M, N, K, (hipStream_t)stream, false, xtype, ytype, nullptr, dcol_scale,
-                   true, drow_scale_out);
+    return run_dev(h, with_quant(dev_call(dX, xtype, db, dY, ytype, ldY, M, N, K, stream), drow_scale_out, dcol_scale));
 }
 
 extern "C" int tcsc_hip_gemm_prelu_dev_actquant(tsg_tcsc *h, const void *dX, int xtype, float *drow_scale_out,
                                                 const float *dcol_scale, const float *db, const float *dalpha,
                                                 void *dY, int ytype, int64_t ldY, int M, int N, int K, void *stream)
 {
-    return run_dev(h, dX, db, dalpha, dY, ldY, M, N, K, (hipStream_t)stream, true, xtype, ytype, nullptr, dcol_scale,
-                   true, drow_scale_out);
+    const Call c = with_prelu(dev_call(dX, xtype, db, dY, ytype, ldY, M, N, K, stream), dalpha);
+    return run_dev(h, with_quant(c, drow_scale_out, dcol_scale));
 }
 
 // Fused RMSNorm + activation quantisation (tsg_norm.h): the _actquant calls on
 // xn = (X * rn[m]) * gamma[k], made by the same two passes -- the row pass finds
 // rn first, the staging pass normalises what it loads before it quantises
-// (Call::norm, Call::dgamma, Call::eps)
+// (Call::norm, XIn::g, Call::eps)
 extern "C" int tcsc_hip_gemm_dev_normquant(tsg_tcsc *h, const void *dX, int xtype, const float *dgamma, float eps,
                                            float *drow_scale_out, const float *dcol_scale, const float *db, void *dY,
                                            int ytype, int64_t ldY, int M, int N, int K, void *stream)
 {
-    return run_dev(h, dX, db, nullptr, dY, ldY, M, N, K, (hipStream_t)stream, false, xtype, ytype, nullptr, dcol_scale,
-                   true, drow_scale_out, true, dgamma, eps);
+    const Call c = with_quant(dev_call(dX, xtype, db, dY, ytype, ldY, M, N, K, stream), drow_scale_out, dcol_scale);
+    return run_dev(h, with_norm(c, dgamma, eps));
 }
 
 extern "C" int tcsc_hip_gemm_prelu_dev_normquant(tsg_tcsc *h, const void *dX, int xtype, const float *dgamma, float eps,
@@ -1549,8 +1575,8 @@ extern "C" int tcsc_hip_gemm_prelu_dev_normquant(tsg_tcsc *h, const void *dX, in
                                                  const float *dalpha, void *dY, int ytype, int64_t ldY, int M, int N,
                                                  int K, void *stream)
 {
-    return run_dev(h, dX, db, dalpha, dY, ldY, M, N, K, (hipStream_t)stream, true, xtype, ytype, nullptr, dcol_scale,
-                   true, drow_scale_out, true, dgamma, eps);
+    const Call c = with_prelu(dev_call(dX, xtype, db, dY, ytype, ldY, M, N, K, stream), dalpha);
+    return run_dev(h, with_norm(with_quant(c, drow_scale_out, dcol_scale), dgamma, eps));
 }
 
 // The descriptor call (include/ternary_spgemm.h tsg_gemm_ex): every device call
@@ -1623,10 +1649,12 @@ extern "C" int tcsc_hip_gemm_dev_ex(tsg_tcsc *h, const tsg_gemm_ex *d, int M, in
         ep.bits |= d->addtype << tsg::kEpiAddShift;
         if (d->dadd == d->dY && d->addtype == d->ytype && d->ldadd == d->ldY) ep.bits |= tsg::kEpiAddIsY;
     }
-    const bool prelu = d->act == TSG_ACT_PRELU, quant = d->in_mode != TSG_IN_PLAIN;
-    return run_dev(h, d->dX, d->db, prelu ? d->dalpha : nullptr, d->dY, d->ldY, M, N, K, (hipStream_t)stream, prelu,
-                   d->xtype, d->ytype, d->drow_scale, d->dcol_scale, quant, d->drow_scale_out,
-                   d->in_mode == TSG_IN_NORMQUANT, d->dgamma, d->eps, ep);
+    Call c = dev_call(d->dX, d->xtype, d->db, d->dY, d->ytype, d->ldY, M, N, K, stream);
+    if (d->act == TSG_ACT_PRELU) c = with_prelu(c, d->dalpha);
+    c.out.rs = d->drow_scale, c.out.cs = d->dcol_scale, c.out.ep = ep;
+    c.quant = d->in_mode != TSG_IN_PLAIN, c.drs_out = d->drow_scale_out;
+    c.norm = d->in_mode == TSG_IN_NORMQUANT, c.in.g = d->dgamma, c.eps = d->eps;
+    return run_dev(h, c);
 }
 
 extern "C" int tcsc_hip_info(const tsg_tcsc *h, tsg_info *o)

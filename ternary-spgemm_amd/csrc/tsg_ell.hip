@@ -601,30 +601,33 @@ __global__ __launch_bounds__(64 * (MT + E / 8)) void tsg_tcsc_ell_pc_kernel(
 
 namespace {
 
+// The launchers below choose LG / RPL / WPG / LA (and the phase of the
+// producer/consumer walk) and hand on the same three values: the caller's X as
+// its element type, the uploaded image and the output block (tsg_internal.h).
 template <typename T, int LG, int RPL, int WPG, int LA>
-int launch_ell_la(const T *X, const uint4 *ent, const uint2 *tab, const float *b, const float *alpha, const float *rs, const float *cs, const Epi &ep, float *Y,
-                  int64_t ldY, int ytype, int M, int N, int K, int C, int nch, int xb, int zr, int prelu, hipStream_t s)
+int launch_ell_la(const T *X, const EllDev &e, const YOut &o)
 {
     constexpr int MT = LG * RPL, CPW = 64 / LG;
-    const int nsg = (N + WPG * CPW - 1) / (WPG * CPW);
-    const int mtiles = (M + MT - 1) / MT;
-    const int steps = nch == 1 ? 1 : 2 * nch;
-    const size_t lds = ell_lds_floats(C, MT, xb, zr) * sizeof(float);
+    const int nsg = (o.N + WPG * CPW - 1) / (WPG * CPW);
+    const int mtiles = (o.M + MT - 1) / MT;
+    const int steps = e.nch == 1 ? 1 : 2 * e.nch;
+    const size_t lds = ell_lds_floats(e.C, MT, e.xb, e.zr) * sizeof(float);
     const dim3 grid((unsigned)(nsg * mtiles)), block(WPG * 64);
-    if (rs || cs || ep.on()) {  // a scaled call, or one with a fused epilogue: the kernel with that epilogue
-        if (ep.on()) ytype |= kYEpi;  // its one test for a fused epilogue (tsg_internal.h)
-        if (prelu)
-            hipLaunchKernelGGL((tsg_tcsc_ell_scaled_kernel<T, LG, RPL, WPG, LA, true>), grid, block, lds, s, X, ent, tab,
-                               b, alpha, rs, cs, ep, Y, ldY, ytype, M, N, K, C, nch, steps, nsg, xb, zr);
-        else
-            hipLaunchKernelGGL((tsg_tcsc_ell_scaled_kernel<T, LG, RPL, WPG, LA, false>), grid, block, lds, s, X, ent, tab,
-                               b, alpha, rs, cs, ep, Y, ldY, ytype, M, N, K, C, nch, steps, nsg, xb, zr);
-    } else if (prelu)
-        hipLaunchKernelGGL((tsg_tcsc_ell_kernel<T, LG, RPL, WPG, LA, true>), grid, block, lds, s, X, ent, tab, b, alpha,
-                           Y, ldY, ytype, M, N, K, C, nch, steps, nsg, xb, zr);
-    else
-        hipLaunchKernelGGL((tsg_tcsc_ell_kernel<T, LG, RPL, WPG, LA, false>), grid, block, lds, s, X, ent, tab, b, alpha,
-                           Y, ldY, ytype, M, N, K, C, nch, steps, nsg, xb, zr);
+    hipStream_t s = (hipStream_t)o.stream;
+    const uint4 *ent = reinterpret_cast<const uint4 *>(e.ent);
+    const uint2 *tab = reinterpret_cast<const uint2 *>(e.tab);
+    float *Y = static_cast<float *>(o.Y);  // elements of ytype; the kernels' epilogue casts (tsg_ytype.h)
+    const int ytype = o.kernel_ytype(false);  // a scaled call runs the kernel with that epilogue: no flag
+    if (o.scaled() || o.ep.on()) {
+        auto *kernel = o.prelu ? tsg_tcsc_ell_scaled_kernel<T, LG, RPL, WPG, LA, true>
+                               : tsg_tcsc_ell_scaled_kernel<T, LG, RPL, WPG, LA, false>;
+        hipLaunchKernelGGL(kernel, grid, block, lds, s, X, ent, tab, o.b, o.alpha, o.rs, o.cs, o.ep, Y, o.ldY, ytype, o.M,
+                           o.N, e.K, e.C, e.nch, steps, nsg, e.xb, e.zr);
+    } else {
+        auto *kernel = o.prelu ? tsg_tcsc_ell_kernel<T, LG, RPL, WPG, LA, true> : tsg_tcsc_ell_kernel<T, LG, RPL, WPG, LA, false>;
+        hipLaunchKernelGGL(kernel, grid, block, lds, s, X, ent, tab, o.b, o.alpha, Y, o.ldY, ytype, o.M, o.N, e.K, e.C,
+                           e.nch, steps, nsg, e.xb, e.zr);
+    }
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -640,17 +643,11 @@ int pick_la()
 }
 
 template <typename T, int LG, int RPL, int WPG>
-int launch_ell_t(const T *X, const uint4 *ent, const uint2 *tab, const float *b, const float *alpha, const float *rs, const float *cs, const Epi &ep, float *Y,
-                 int64_t ldY, int ytype, int M, int N, int K, int C, int nch, int xb, int zr, int prelu, hipStream_t s)
+int launch_ell_t(const T *X, const EllDev &e, const YOut &o)
 {
-    if (pick_la() == 2)
-        return launch_ell_la<T, LG, RPL, WPG, 2>(X, ent, tab, b, alpha, rs, cs, ep, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
-    return launch_ell_la<T, LG, RPL, WPG, 1>(X, ent, tab, b, alpha, rs, cs, ep, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
+    if (pick_la() == 2) return launch_ell_la<T, LG, RPL, WPG, 2>(X, e, o);
+    return launch_ell_la<T, LG, RPL, WPG, 1>(X, e, o);
 }
-
-}  // namespace
-
-namespace {
 
 // Waves per workgroup: 16 or 8 when the grid is then one round that still
 // gives (nearly) every CU a workgroup (kEllWideWgs ... 256 x the workgroups
@@ -666,36 +663,31 @@ namespace {
 constexpr int64_t kEllWideWgs = 224;  // 7/8 of the CUs
 
 template <typename T, int LG, int RPL>
-int launch_lg(const T *X, const uint4 *e, const uint2 *t, const float *b, const float *alpha, const float *rs, const float *cs, const Epi &ep, float *Y,
-              int64_t ldY, int ytype, int M, int N, int K, int C, int nch, int xb, int zr, int prelu, hipStream_t s)
+int launch_lg(const T *X, const EllDev &e, const YOut &o)
 {
     constexpr int MT = LG * RPL, CPW = 64 / LG;
-    const int64_t waves = (int64_t)((N + CPW - 1) / CPW) * ((M + MT - 1) / MT);
-    const int64_t per_cu = std::max<int64_t>(1, 163840 / ((int64_t)ell_lds_floats(C, MT, xb, zr) * 4));
+    const int64_t waves = (int64_t)((o.N + CPW - 1) / CPW) * ((o.M + MT - 1) / MT);
+    const int64_t per_cu = std::max<int64_t>(1, 163840 / ((int64_t)ell_lds_floats(e.C, MT, e.xb, e.zr) * 4));
     static const int env_wpg = [] {  // TSG_ELL_WPG=4/8/16: waves per workgroup (A/B)
         const char *v = knob_value("TSG_ELL_WPG");
         return v ? atoi(v) : 0;
     }();
-    if (env_wpg == 4) return launch_ell_t<T, LG, RPL, 4>(X, e, t, b, alpha, rs, cs, ep, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
+    if (env_wpg == 4) return launch_ell_t<T, LG, RPL, 4>(X, e, o);
     if constexpr (RPL <= 2) {
-        if (env_wpg == 8) return launch_ell_t<T, LG, RPL, 8>(X, e, t, b, alpha, rs, cs, ep, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
-        if (env_wpg == 16)
-            return launch_ell_t<T, LG, RPL, 16>(X, e, t, b, alpha, rs, cs, ep, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
+        if (env_wpg == 8) return launch_ell_t<T, LG, RPL, 8>(X, e, o);
+        if (env_wpg == 16) return launch_ell_t<T, LG, RPL, 16>(X, e, o);
     }
     if constexpr (RPL <= 2) {
         auto one_round = [&](int64_t wpg) {  // >= 7/8 of the CUs busy, no second round
             const int64_t wgs = (waves + wpg - 1) / wpg;
             return wgs >= kEllWideWgs && wgs <= 256 * per_cu;
         };
-        if (one_round(16))
-            return launch_ell_t<T, LG, RPL, 16>(X, e, t, b, alpha, rs, cs, ep, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
-        if (one_round(8)) return launch_ell_t<T, LG, RPL, 8>(X, e, t, b, alpha, rs, cs, ep, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
-        if (waves > 256 * per_cu * 8)
-            return launch_ell_t<T, LG, RPL, 16>(X, e, t, b, alpha, rs, cs, ep, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
-        if (waves > 256 * per_cu * 4)
-            return launch_ell_t<T, LG, RPL, 8>(X, e, t, b, alpha, rs, cs, ep, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
+        if (one_round(16)) return launch_ell_t<T, LG, RPL, 16>(X, e, o);
+        if (one_round(8)) return launch_ell_t<T, LG, RPL, 8>(X, e, o);
+        if (waves > 256 * per_cu * 8) return launch_ell_t<T, LG, RPL, 16>(X, e, o);
+        if (waves > 256 * per_cu * 4) return launch_ell_t<T, LG, RPL, 8>(X, e, o);
     }
-    return launch_ell_t<T, LG, RPL, 4>(X, e, t, b, alpha, rs, cs, ep, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
+    return launch_ell_t<T, LG, RPL, 4>(X, e, o);
 }
 
 // lanes per column of an M tile: the default, or TSG_ELL_LG (diagnostic sweeps)
@@ -715,26 +707,23 @@ constexpr size_t pc_lds(int C)
 }
 
 template <typename T, int MT, int E>
-int launch_pc_t(const T *X, const uint4 *ent, const uint2 *tab, const float *b, const float *alpha, const float *rs, const float *cs, const Epi &ep, float *Y,
-                int64_t ldY, int ytype, int M, int N, int K, int C, int prelu, hipStream_t s)
+int launch_pc_t(const T *X, const EllDev &e, const YOut &o)
 {
     using S = PcShape<MT, E>;
-    const int nsg = (N + 63) / 64;
-    const int mtiles = (M + MT - 1) / MT;
-    const size_t lds = pc_lds<MT, E>(C);
+    const int nsg = (o.N + 63) / 64;
+    const int mtiles = (o.M + MT - 1) / MT;
+    const size_t lds = pc_lds<MT, E>(e.C);
     const dim3 grid((unsigned)(nsg * mtiles)), block(S::NT);
-    if (prelu)
-        hipLaunchKernelGGL((tsg_tcsc_ell_pc_kernel<T, MT, E, true>), grid, block, lds, s, X, ent, tab, b, alpha, rs, cs, ep, Y, ldY, ytype, M,
-                           N, K, C, nsg);
-    else
-        hipLaunchKernelGGL((tsg_tcsc_ell_pc_kernel<T, MT, E, false>), grid, block, lds, s, X, ent, tab, b, alpha, rs, cs, ep, Y, ldY, ytype,
-                           M, N, K, C, nsg);
+    hipStream_t s = (hipStream_t)o.stream;
+    const uint4 *ent = reinterpret_cast<const uint4 *>(e.ent);
+    const uint2 *tab = reinterpret_cast<const uint2 *>(e.tab);
+    float *Y = static_cast<float *>(o.Y);  // elements of ytype; the kernel's epilogue casts (tsg_ytype.h)
+    const int ytype = o.kernel_ytype(true);  // the kernel's one test for a scaled call or a fused epilogue
+    auto *kernel = o.prelu ? tsg_tcsc_ell_pc_kernel<T, MT, E, true> : tsg_tcsc_ell_pc_kernel<T, MT, E, false>;
+    hipLaunchKernelGGL(kernel, grid, block, lds, s, X, ent, tab, o.b, o.alpha, o.rs, o.cs, o.ep, Y, o.ldY, ytype, o.M, o.N,
+                       e.K, e.C, nsg);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
-
-}  // namespace
-
-namespace {
 
 // Phase length E (entries of every chain per barrier).  64 while every
 // workgroup is resident at once (M * ceil(N / 64) <= 256: one per CU), the
@@ -770,85 +759,59 @@ size_t ell_pc_lds_bytes(int variant, int C)
     return variant == 0 ? pc_lds<1, 32>(C) : 0;
 }
 
-int launch_tcsc_ell_pc(int variant, const void *X, int xtype, const uint32_t *ent, const uint32_t *tab, const float *b,
-                       const float *alpha, const float *rs, const float *cs, const Epi &ep, void *Yv, int ytype, int64_t ldY, int M, int N, int K, int C, int nch,
-                       int prelu, void *stream)
+int launch_tcsc_ell_pc(int variant, const void *X, int xtype, const EllDev &e, const YOut &o)
 {
-    float *Y = static_cast<float *>(Yv);  // elements of ytype; the kernels' epilogue casts (tsg_ytype.h)
-    if (rs || cs) ytype |= kYScaled;      // the kernel's one test for a scaled call (tsg_internal.h)
-    if (ep.on()) ytype |= kYEpi;          // ... and for one with a fused epilogue
     // one stream per column, X chunk + ring within a workgroup's LDS
-    if (nch != 1 || ell_pc_lds_bytes(variant, C) == 0 || ell_pc_lds_bytes(variant, C) > kLdsBytes) return -2;
-    hipStream_t s = (hipStream_t)stream;
-    const uint4 *e = reinterpret_cast<const uint4 *>(ent);
-    const uint2 *t = reinterpret_cast<const uint2 *>(tab);
-    const int phase = pc_phase(M, N, C);
+    if (e.nch != 1 || ell_pc_lds_bytes(variant, e.C) == 0 || ell_pc_lds_bytes(variant, e.C) > kLdsBytes) return -2;
+    const int phase = pc_phase(o.M, o.N, e.C);
     return with_xtype(X, xtype, [&](auto *x) {
         using T = std::remove_cv_t<std::remove_pointer_t<decltype(x)>>;
         switch (phase) {
-        case 16: return launch_pc_t<T, 1, 16>(x, e, t, b, alpha, rs, cs, ep, Y, ldY, ytype, M, N, K, C, prelu, s);
-        case 64: return launch_pc_t<T, 1, 64>(x, e, t, b, alpha, rs, cs, ep, Y, ldY, ytype, M, N, K, C, prelu, s);
-        default: return launch_pc_t<T, 1, 32>(x, e, t, b, alpha, rs, cs, ep, Y, ldY, ytype, M, N, K, C, prelu, s);  // 1 consumer, 4 producers
+        case 16: return launch_pc_t<T, 1, 16>(x, e, o);
+        case 64: return launch_pc_t<T, 1, 64>(x, e, o);
+        default: return launch_pc_t<T, 1, 32>(x, e, o);  // 1 consumer, 4 producers
         }
     });
 }
 
-namespace {
-
-template <typename T>
-int launch_ell_variant(int variant, const T *X, const uint4 *e, const uint2 *t, const float *b, const float *alpha, const float *rs, const float *cs,
-                       const Epi &ep, float *Y, int64_t ldY, int ytype, int M, int N, int K, int C, int nch, int xb, int zr, int prelu,
-                       hipStream_t s)
+int launch_tcsc_ell(int variant, const void *Xv, int xtype, const EllDev &e, const YOut &o)
 {
-#define TSG_ELL_LG(lg, rpl) \
-    case lg: return launch_lg<T, lg, rpl>(X, e, t, b, alpha, rs, cs, ep, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s)
-    switch (variant) {
-    case 0: return launch_ell_t<T, 1, 1, 1>(X, e, t, b, alpha, rs, cs, ep, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);  // MT = 1
-    case 1:                                                                                   // MT = 4
-        switch (pick_lg(4)) {
-            TSG_ELL_LG(4, 1);
-            TSG_ELL_LG(2, 2);
-        default: return -2;
-        }
-    case 2:                                                                                   // MT = 8
-        switch (pick_lg(4)) {
-            TSG_ELL_LG(8, 1);
-            TSG_ELL_LG(4, 2);
-            TSG_ELL_LG(2, 4);
-        default: return -2;
-        }
-    case 3:                                                                                   // MT = 16
-        switch (pick_lg(8)) {
-            TSG_ELL_LG(8, 2);
-            TSG_ELL_LG(16, 1);
-        default: return -2;
-        }
-    case 4:                                                                                   // MT = 32
-        switch (pick_lg(16)) {
-            TSG_ELL_LG(16, 2);
-        default: return -2;
-        }
-    default: return -2;
-    }
-#undef TSG_ELL_LG
-}
-
-}  // namespace
-
-int launch_tcsc_ell(int variant, const void *X, int xtype, const uint32_t *ent, const uint32_t *tab, const float *b,
-                    const float *alpha, const float *rs, const float *cs, const Epi &ep, void *Yv, int ytype, int64_t ldY, int M, int N, int K, int C, int nch, int xb,
-                    int zr, int prelu, void *stream)
-{
-    float *Y = static_cast<float *>(Yv);  // elements of ytype; the kernels' epilogue casts (tsg_ytype.h)
     // the second X^T copy and the bank-window schedule serve the 8-row tile's
     // 4-lane columns only (tsg_host.cpp build_ell_image)
-    if ((xb || zr != 1) && (variant != 2 || pick_lg(4) != 4)) return -2;
-    hipStream_t s = (hipStream_t)stream;
-    const uint4 *e = reinterpret_cast<const uint4 *>(ent);
-    const uint2 *t = reinterpret_cast<const uint2 *>(tab);
-    return with_xtype(X, xtype, [&](auto *x) {
-        return launch_ell_variant(variant, x, e, t, b, alpha, rs, cs, ep, Y, ldY, ytype, M, N, K, C, nch, xb, zr, prelu, s);
+    if ((e.xb || e.zr != 1) && (variant != 2 || pick_lg(4) != 4)) return -2;
+#define TSG_ELL_LG(lg, rpl) case lg: return launch_lg<T, lg, rpl>(X, e, o)
+    return with_xtype(Xv, xtype, [&](auto *X) {
+        using T = std::remove_cv_t<std::remove_pointer_t<decltype(X)>>;
+        switch (variant) {
+        case 0: return launch_ell_t<T, 1, 1, 1>(X, e, o);  // MT = 1
+        case 1:                                            // MT = 4
+            switch (pick_lg(4)) {
+                TSG_ELL_LG(4, 1);
+                TSG_ELL_LG(2, 2);
+            default: return -2;
+            }
+        case 2:                                            // MT = 8
+            switch (pick_lg(4)) {
+                TSG_ELL_LG(8, 1);
+                TSG_ELL_LG(4, 2);
+                TSG_ELL_LG(2, 4);
+            default: return -2;
+            }
+        case 3:                                            // MT = 16
+            switch (pick_lg(8)) {
+                TSG_ELL_LG(8, 2);
+                TSG_ELL_LG(16, 1);
+            default: return -2;
+            }
+        case 4:                                            // MT = 32
+            switch (pick_lg(16)) {
+                TSG_ELL_LG(16, 2);
+            default: return -2;
+            }
+        default: return -2;
+        }
     });
+#undef TSG_ELL_LG
 }
 
 }  // namespace tsg

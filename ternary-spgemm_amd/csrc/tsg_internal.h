@@ -29,21 +29,6 @@ inline bool x_quad_aligned(const void *X, int xtype) { return ((uintptr_t)X & (4
 // (tsg_ytype.h).  ldY counts elements of this type; the planner, the work
 // buffer and the staging passes do not look at it.
 enum YType { kYF32 = 0, kYF16 = 1, kYBF16 = 2 };
-// Flag the launchers of the image dispatchers and of the producer/consumer
-// walk set in the kernel's ytype argument when the call passes an epilogue
-// scale (tsg_scale.h): the test for a scaled call reads a register the
-// epilogue holds anyway, and the dispatchers' fp32 path stays behind the one
-// test `ytype != kYF32`.  (The ELL walk has a kernel of its own for scaled
-// calls, tsg_tcsc_ell_scaled_kernel; rx tests the two pointers.)
-constexpr int kYScaled = 0x100;
-// A second flag next to it, set by the launchers of every kernel that stores Y
-// when the call has a fused epilogue (tsg_epilogue.h: ReLU / ReLU^2, a gate
-// multiply, a residual add; tcsc_hip_gemm_dev_ex).  Such a call takes a branch
-// of its own inside the kernels' `ytype != kYF32` test, which serves the
-// scales and every Y type too; a call without one never sets it and runs the
-// code it ran before.
-constexpr int kYEpi = 0x200;
-constexpr int kYTypeMask = 0xff;
 inline bool ytype_ok(int ytype) { return ytype >= kYF32 && ytype <= kYBF16; }
 inline size_t ytype_size(int ytype) { return ytype == kYF32 ? 4 : 2; }
 
@@ -65,6 +50,55 @@ struct Epi {
     int64_t ldadd = 0;
     int bits = 0;
     bool on() const { return (bits & kEpiActMask) != 0 || mul != nullptr || add != nullptr; }
+};
+
+// Two flags next to the type in a kernel's ytype argument; YOut::kernel_ytype
+// below is the one place that sets them, kYTypeMask gives the type back.
+// kYScaled: the call passes an epilogue scale (tsg_scale.h).  Only the image
+// dispatchers and the producer/consumer walk ask for it: their test for a
+// scaled call reads a register the epilogue holds anyway, and the dispatchers'
+// fp32 path stays behind the one test `ytype != kYF32`.  (The ELL walk has a
+// kernel of its own for scaled calls, tsg_tcsc_ell_scaled_kernel; rx tests the
+// two pointers.)  kYEpi: the call has a fused epilogue (tsg_epilogue.h: ReLU /
+// ReLU^2, a gate multiply, a residual add; tcsc_hip_gemm_dev_ex), whatever the
+// kernel.  Such a call takes a branch of its own inside the kernels' `ytype !=
+// kYF32` test, which serves the scales and every Y type too; a call without one
+// never sets it and runs the code it ran before.
+constexpr int kYScaled = 0x100;
+constexpr int kYEpi = 0x200;
+constexpr int kYTypeMask = 0xff;
+
+// The output block: what the launcher of every kernel that stores Y is given.
+// Y: [M, N] elements of ytype (YType), ldY of them from one row to the next
+// (>= N); rs, cs: the epilogue scales (float[M], float[N]; either may be null:
+// tsg_scale.h; rs of an actquant call: the scratch's deq); ep: the fused epilogue.
+struct YOut {
+    const float *b = nullptr, *alpha = nullptr, *rs = nullptr, *cs = nullptr;
+    Epi ep;
+    void *Y = nullptr;
+    int ytype = kYF32;
+    int64_t ldY = 0;
+    int M = 0, N = 0;
+    bool prelu = false;
+    void *stream = nullptr;
+    bool scaled() const { return rs != nullptr || cs != nullptr; }
+    // the ytype argument as a kernel receives it; wants_scaled: this kernel tests kYScaled
+    int kernel_ytype(bool wants_scaled) const { return ytype | (wants_scaled && scaled() ? kYScaled : 0) | (ep.on() ? kYEpi : 0); }
+};
+
+// The input block: what the passes that read the caller's X are given.  X is
+// M x K row-major of element type xtype (XType); the staged copies are fp32.
+// inv (float[M]; null: none): the staging pass quantises every value it loads,
+// xquant(v, inv[m]) (tsg_actquant.h; an actquant call, never an int8 X).
+// rn (float[M], with inv) and g (float[K] or null): it normalises first,
+// xquant(xnorm(v, rn[m], g[k]), inv[m]) (tsg_norm.h; a normquant call).
+// launch_row_absmax writes inv and rn, the staging passes read them.
+struct XIn {
+    const void *X = nullptr;
+    int xtype = kXF32;
+    int M = 0, K = 0;
+    float *inv = nullptr, *rn = nullptr;
+    const float *g = nullptr;
 };
 
 // ---------------------------------------------------------------------------
@@ -272,27 +306,30 @@ struct JitModule {
                      bool rows64 = false, bool half = false, bool pair = false);  // "" on success
     void unload();
 };
-// ldY: elements of Y's type (ytype, YType) from one Y row to the next (>= N;
-// every kernel below takes both);
-// xrow > 0: the 64-row image stages straight from X (xrow floats per row);
-// lastadj: bytes the row layout's last chunk starts below its slot (direct X);
-// xtouch: the per-group code touches (v[lane128 + 1]) spread over the lines;
-// tnear: the code touches' window starts at the step's own position;
-// rs, cs: the epilogue scales of the _scaled calls (float[M], float[N]; either
-// may be null: tsg_scale.h), taken by every kernel below that stores Y;
-// ep: the call's fused epilogue (Epi above; tsg_epilogue.h), likewise
-int launch_tcsc_jit(const JitModule &jm, const float *XT, int Mp, const uint32_t *wcode,
-                    const float *b, const float *alpha, const float *rs, const float *cs, const Epi &ep, void *Y, int ytype,
-                    int64_t ldY, int M, int N, int Npad, int nch, int prelu, uint32_t *status, int tile_cols,
-                    int waves, int gn, int gm, int tmask, void *stream, int tile_m = kJitTileM, int xrow = 0, int lastadj = 0, int xtouch = 0,
-                    int tnear = 0, int loop_wgs = 0, int lflags = 0, int *launched = nullptr);
-// loop_wgs > 0: that many workgroups, each looping over the logical ids b,
-// b + loop_wgs, ... (the 64-row image's 8-wave dispatcher only; tsg_plan.h
-// loop_wgs); 0: one workgroup per id.  lflags (diagnostic build only,
-// TSG_JIT_DIAG; results WRONG): nostore -- the dispatcher skips its epilogue
-// (bit 30 of its lstep argument); onetile -- the launch covers only its first
-// loop_wgs logical ids.  launched (may be null): {workgroups, logical ids} of
-// the launch as passed to the runtime and the kernel
+// The launch geometry of one dispatcher call: the image (wcode, Npad, nch,
+// tile_cols, tile_m), the X^T it reads (Mp rows per K row), the workgroups
+// (waves each; gn, gm, tmask: the id map of tsg_jit_map.h) and the plan's choices.
+struct JitLaunch {
+    int Mp = 0;
+    const uint32_t *wcode = nullptr;
+    int Npad = 0, nch = 0;
+    uint32_t *status = nullptr;
+    int tile_cols = kJitTileCols, waves = kJitWaves, gn = 0, gm = 0, tmask = 0, tile_m = kJitTileM;
+    int xrow = 0;      // > 0: the 64-row image stages straight from X (xrow floats per row)
+    int lastadj = 0;   // bytes the row layout's last chunk starts below its slot (direct X)
+    int xtouch = 0;    // the per-group code touches (v[lane128 + 1]) spread over the lines
+    int tnear = 0;     // the code touches' window starts at the step's own position
+    // > 0: that many workgroups, each looping over the logical ids b, b + loop_wgs,
+    // ... (the 64-row image's 8-wave dispatcher only; tsg_plan.h loop_wgs); 0: one per id
+    int loop_wgs = 0;
+    // diagnostic build only (TSG_JIT_DIAG; results WRONG): nostore -- the dispatcher
+    // skips its epilogue (bit 30 of its lstep argument); onetile -- the launch
+    // covers only its first loop_wgs logical ids
+    int lflags = 0;
+};
+// XT: the staged fp32 copy, or with g.xrow the caller's row-major fp32 X;
+// launched: {workgroups, logical ids} of the launch as passed to the runtime and the kernel
+int launch_tcsc_jit(const JitModule &jm, const void *XT, const JitLaunch &g, const YOut &o, int *launched);
 constexpr int kJitDiagNoStore = 1 << 30, kJitDiagOneTile = 1 << 29;
 int launch_jit_probe(const JitModule &jm, uint32_t *status, void *stream);
 
@@ -337,17 +374,19 @@ __host__ __device__ constexpr int ell_lds_floats(int C, int MT, int xb, int zr =
 constexpr int kEllSchedZeroRows = 8;
 void build_ell_image(const int32_t *csp, const int32_t *csn, const int32_t *rip, const int32_t *rin, int K, int N,
                      int Cmax, int MT, EllImage &img, int copies = 1, bool sched = false);
-int launch_tcsc_ell(int variant, const void *X, int xtype, const uint32_t *ent, const uint32_t *tab, const float *b,
-                    const float *alpha, const float *rs, const float *cs, const Epi &ep, void *Y, int ytype, int64_t ldY, int M, int N, int K, int C, int nch, int xb,
-                    int zr, int prelu, void *stream);
+// the uploaded image of a variant, as the two walks' launchers take it (K: W's rows)
+struct EllDev {
+    const uint32_t *ent = nullptr, *tab = nullptr;
+    int K = 0, C = 0, nch = 0, xb = 0, zr = 1;
+};
+// X: the caller's, M x K row-major of xtype (the walks read it in place)
+int launch_tcsc_ell(int variant, const void *X, int xtype, const EllDev &e, const YOut &o);
 // the producer/consumer walk (tsg_tcsc_ell_pc_kernel) of variant 0 (M = 1) when
 // K fits one chunk and the chunk plus its LDS ring fit kLdsBytes
 // (ell_pc_lds_bytes; 0 = no such variant); -2 = not available for this image
 constexpr size_t kLdsBytes = 160 * 1024;
 size_t ell_pc_lds_bytes(int variant, int C);
-int launch_tcsc_ell_pc(int variant, const void *X, int xtype, const uint32_t *ent, const uint32_t *tab, const float *b,
-                       const float *alpha, const float *rs, const float *cs, const Epi &ep, void *Y, int ytype, int64_t ldY, int M, int N, int K, int C, int nch,
-                       int prelu, void *stream);
+int launch_tcsc_ell_pc(int variant, const void *X, int xtype, const EllDev &e, const YOut &o);
 
 // Environment knobs (csrc/tsg_knobs.cpp): A/B studies and tests, none of
 // which changes a result.  knob_check: "" when every set knob has an
@@ -371,34 +410,26 @@ int encode_count(const int32_t *dW, int K, int N, int32_t *d_csp, int32_t *d_csn
 int encode_fill(const int32_t *dW, int K, int N, const int32_t *d_csp, const int32_t *d_csn, int32_t *d_rip,
                 int32_t *d_rin, void *stream);
 
-// Kernel launchers (csrc/tcsc_kernels.hip).  All enqueue on `stream`.  X is M x
-// K row-major of element type xtype (XType); the staged copies are fp32.
-// inv (float[M], default none): the staging pass quantises every value it
-// loads, xquant(v, inv[m]) (tsg_actquant.h; an actquant call, never an int8 X).
-// rn (float[M], with inv; default none) and g (float[K] or null): it normalises
-// first, xquant(xnorm(v, rn[m], g[k]), inv[m]) (tsg_norm.h; a normquant call).
-int launch_transpose(const void *X, int xtype, float *XT, int M, int K, int Mp, int Kp, void *stream,
-                     const float *inv = nullptr, const float *rn = nullptr, const float *g = nullptr);
+// Kernel launchers (csrc/tcsc_kernels.hip).  The staging passes read the input
+// block (XIn above) and write fp32; the rx walk stores through the output block
+// (YOut above).
+int launch_transpose(const XIn &in, float *XT, int Mp, int Kp, void *stream);
 // X [M][K] -> X^T in the k-pair layout of the jit kernel (Kp even, Mp even)
-int launch_transpose_pairs(const void *X, int xtype, float *XP, int M, int K, int Mp, int Kp, void *stream,
-                           const float *inv = nullptr, const float *rn = nullptr, const float *g = nullptr);
+int launch_transpose_pairs(const XIn &in, float *XP, int Mp, int Kp, void *stream);
 // X [M][K] -> the blocked k-quad layout of the 64-row image (Mp % 64 == 0, Kp % 192 == 0;
 // piece_rows 16 or 8, kJit64R16Flag), or with piece_rows 0 its row layout's
 // staged copy (kJit64RowFlag; Kp % 188 == 0)
-int launch_transpose_quads(const void *X, int xtype, float *XQ, int M, int K, int Mp, int Kp, int piece_rows,
-                           void *stream, int chunk = kJit64Chunk, const float *inv = nullptr,
-                           const float *rn = nullptr, const float *g = nullptr);
-// The row pass of an actquant call (tsg_row_absmax_kernel): inv[m] = 127 / a and
-// deq[m] = a / 127, a = max(max_k |X[m,k]|, 1e-5), for every row; deq also to
+int launch_transpose_quads(const XIn &in, float *XQ, int Mp, int Kp, int piece_rows, int chunk, void *stream);
+// The row pass of an actquant call (tsg_row_absmax_kernel): in.inv[m] = 127 / a
+// and deq[m] = a / 127, a = max(max_k |X[m,k]|, 1e-5), for every row; deq also to
 // out (may be null); q8 (may be null): the int8 q of all of X, row-major [M][K],
-// for the small-M walks.  X is fp32, fp16 or bf16.  rn (float[M], default none):
-// the row pass of a normquant call -- rn[m] = 1 / sqrtf(mean_k X[m,k]^2 + eps) in
-// the summation order of tsg_norm.h is stored too, and the maximum and q are
-// taken of (X[m,k] * rn[m]) * g[k] (g may be null).
-int launch_row_absmax(const void *X, int xtype, int M, int K, float *inv, float *deq, float *out, int8_t *q8,
-                      void *stream, float *rn = nullptr, const float *g = nullptr, float eps = 0.0f);
-int launch_tcsc_rx(const float *XT, int Mp, const uint32_t *wstart, const uint32_t *ent,
-                   const float *b, const float *alpha, const float *rs, const float *cs, const Epi &ep, void *Y, int ytype,
-                   int64_t ldY, int M, int N, int Npad, int nch, int prelu, void *stream);
+// for the small-M walks.  X is fp32, fp16 or bf16.  With in.rn the row pass of a
+// normquant call -- rn[m] = 1 / sqrtf(mean_k X[m,k]^2 + eps) in the summation
+// order of tsg_norm.h is stored too, and the maximum and q are taken of
+// (X[m,k] * rn[m]) * g[k] (in.g may be null).
+int launch_row_absmax(const XIn &in, float *deq, float *out, int8_t *q8, float eps, void *stream);
+// wstart, ent, Npad, nch: the rx image (RxImage above), uploaded
+int launch_tcsc_rx(const float *XT, int Mp, const uint32_t *wstart, const uint32_t *ent, int Npad, int nch,
+                   const YOut &o);
 
 }  // namespace tsg

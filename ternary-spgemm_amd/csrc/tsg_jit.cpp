@@ -1130,34 +1130,29 @@ int launch_jit_probe(const JitModule &jm, uint32_t *status, void *stream)
     return e == hipSuccess ? 0 : -1;
 }
 
-int launch_tcsc_jit(const JitModule &jm, const float *XT, int Mp, const uint32_t *wcode, const float *b,
-                    const float *alpha, const float *rs, const float *cs, const Epi &ep, void *Y, int ytype,
-                    int64_t ldY, int M, int N, int Npad, int nch, int prelu, uint32_t *status, int tile_cols, int waves, int gn, int gm,
-                    int tmask, void *stream, int tile_m, int xrow, int lastadj, int xtouch, int tnear, int loop_wgs,
-                    int lflags, int *launched)
+int launch_tcsc_jit(const JitModule &jm, const void *XT, const JitLaunch &g, const YOut &o, int *launched)
 {
-    int mtiles = Mp / tile_m, ntiles = Npad / tile_cols;
+    int mtiles = g.Mp / g.tile_m, ntiles = g.Npad / g.tile_cols;
     // one workgroup per logical id, or loop_wgs workgroups that stride over
     // the ids (the looping dispatcher, tsg_jit_kernel.hip; tsg_plan.cpp loop_wgs)
     int ltiles = mtiles * ntiles;
-    const int grid = loop_wgs > 0 && loop_wgs < ltiles ? loop_wgs : ltiles;
+    const int grid = g.loop_wgs > 0 && g.loop_wgs < ltiles ? g.loop_wgs : ltiles;
     int lstep = grid;
 #ifdef TSG_DIAG
-    if (lflags & kJitDiagOneTile) ltiles = grid;  // one round of the same shape (results WRONG)
-    lstep |= lflags & kJitDiagNoStore;
-#else
-    (void)lflags;
+    if (g.lflags & kJitDiagOneTile) ltiles = grid;  // one round of the same shape (results WRONG)
+    lstep |= g.lflags & kJitDiagNoStore;
 #endif
-    if (rs || cs) ytype |= kYScaled;  // the dispatcher's one test ahead of its fp32 path (tsg_jit_kernel.hip)
-    if (ep.on()) ytype |= kYEpi;      // likewise: a call with a fused epilogue (tsg_epilogue.h)
-    void *params[] = {(void *)&XT, (void *)&Mp, (void *)&wcode, (void *)&b, (void *)&alpha, (void *)&Y,
-                      (void *)&M, (void *)&N, (void *)&nch, (void *)&mtiles, (void *)&ntiles, (void *)&prelu,
-                      (void *)&status, (void *)&gn, (void *)&gm, (void *)&tmask, (void *)&xrow, (void *)&lastadj,
-                      (void *)&xtouch, (void *)&tnear, (void *)&ldY, (void *)&ytype, (void *)&rs, (void *)&cs,
-                      (void *)&ep, (void *)&ltiles, (void *)&lstep};
-    if (launched) launched[0] = grid, launched[1] = ltiles;
-    hipError_t e = hipModuleLaunchKernel((hipFunction_t)jm.function, (unsigned)grid, 1, 1,
-                                         (unsigned)waves * 64u, 1, 1, 0, (hipStream_t)stream, params, nullptr);
+    // both flags: the dispatcher's one test ahead of its fp32 path (tsg_jit_kernel.hip)
+    int ytype = o.kernel_ytype(true), prelu = o.prelu ? 1 : 0;
+    // (the order and the types are the dispatcher's formal list: tsg_jit_args_* markers)
+    void *params[] = {(void *)&XT, (void *)&g.Mp, (void *)&g.wcode, (void *)&o.b, (void *)&o.alpha, (void *)&o.Y,
+                      (void *)&o.M, (void *)&o.N, (void *)&g.nch, (void *)&mtiles, (void *)&ntiles, (void *)&prelu,
+                      (void *)&g.status, (void *)&g.gn, (void *)&g.gm, (void *)&g.tmask, (void *)&g.xrow,
+                      (void *)&g.lastadj, (void *)&g.xtouch, (void *)&g.tnear, (void *)&o.ldY, (void *)&ytype,
+                      (void *)&o.rs, (void *)&o.cs, (void *)&o.ep, (void *)&ltiles, (void *)&lstep};
+    launched[0] = grid, launched[1] = ltiles;
+    hipError_t e = hipModuleLaunchKernel((hipFunction_t)jm.function, (unsigned)grid, 1, 1, (unsigned)g.waves * 64u, 1, 1,
+                                         0, (hipStream_t)o.stream, params, nullptr);
     return e == hipSuccess ? 0 : -1;
 }
 
