@@ -112,6 +112,10 @@ int tcsc_hip_gemm(tsg_tcsc *h, const float *X, const float *b, float *Y, int M, 
  * the call's copies then DMA directly instead of through the runtime's
  * pin-on-the-fly staging.  The buffer must stay allocated until
  * tcsc_hip_host_unregister.  Unregistered (pageable) buffers keep working.
+ * Where the runtime cannot page-lock memory the process already owns (some
+ * virtual machines), tcsc_hip_host_register returns TSG_ERR_HIP with a
+ * message and leaves no HIP error behind: later calls and launches of the
+ * thread are unaffected, and the buffer is used as a pageable one.
  * Extension: no reference counterpart. */
 int tcsc_hip_host_register(void *p, size_t bytes);
 int tcsc_hip_host_unregister(void *p);

@@ -38,9 +38,15 @@ def main():
 
     for chunks in (1, 4, 8, 12, 16, 0):
         run("pageable", chunks)
-    with T.registered_host(X, Y):  # tcsc_hip_host_register: the caller's buffers page-locked once
+    if T.host_register_supported():
+        with T.registered_host(X, Y):  # tcsc_hip_host_register: the caller's buffers page-locked once
+            for chunks in (1, 16, 0):
+                run("registered", chunks)
+    else:  # no page-locking of memory the process already owns here: X and Y allocated page-locked
+        X = torch.from_numpy(X).pin_memory().numpy()
+        Y = torch.empty((M, N), dtype=torch.float32, pin_memory=True).numpy()
         for chunks in (1, 16, 0):
-            run("registered", chunks)
+            run("allocated page-locked", chunks)
 
 
 if __name__ == "__main__":

@@ -1274,18 +1274,31 @@ extern "C" int tcsc_hip_call_tile_rows(const tsg_tcsc *h, int M)
 // Opt-in page-locking of a caller's host buffer (X or Y of repeated
 // host-pointer calls): the copies of the pipeline then DMA straight from / to
 // it instead of the runtime's pin-on-the-fly staging.  The caller keeps the
-// buffer alive until tcsc_hip_host_unregister.
+// buffer alive until tcsc_hip_host_unregister.  Some machines (virtual ones
+// among them) cannot page-lock memory the process already owns: the runtime
+// then also keeps the error for the thread's next launch to report, so a
+// refusal is taken off (hipGetLastError) before it is returned, and the
+// caller goes on with the pageable buffer.
 extern "C" int tcsc_hip_host_register(void *p, size_t bytes)
 {
     if (!p || bytes == 0) return fail(TSG_ERR_ARG, "tcsc_hip_host_register: null pointer or zero size");
-    HIP_TRY(hipHostRegister(p, bytes, hipHostRegisterDefault));
+    const hipError_t e = hipHostRegister(p, bytes, hipHostRegisterDefault);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(TSG_ERR_HIP, std::string("tcsc_hip_host_register: hipHostRegister: ") + hipGetErrorString(e) +
+                                     " (the buffer stays pageable and keeps working)");
+    }
     return TSG_OK;
 }
 
 extern "C" int tcsc_hip_host_unregister(void *p)
 {
     if (!p) return fail(TSG_ERR_ARG, "tcsc_hip_host_unregister: null pointer");
-    HIP_TRY(hipHostUnregister(p));
+    const hipError_t e = hipHostUnregister(p);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(TSG_ERR_HIP, std::string("tcsc_hip_host_unregister: hipHostUnregister: ") + hipGetErrorString(e));
+    }
     return TSG_OK;
 }
 

@@ -28,6 +28,7 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TSG_LIB") or os.path.join(PKG_DIR, "lib", "libternary_spgemm.so")
 
 TSG_OK = 0
+TSG_ERR_HIP = 2
 _ERRNAMES = {1: "TSG_ERR_ARG", 2: "TSG_ERR_HIP", 3: "TSG_ERR_NOMEM", 4: "TSG_ERR_NODEV",
              5: "TSG_ERR_RANGE"}
 
@@ -603,9 +604,29 @@ def gemm_ex_check(desc, M: int, N: int, K: int) -> None:
     _check(lib().tsg_gemm_ex_check(None if desc is None else C.byref(desc), M, N, K), "tsg_gemm_ex_check")
 
 
+_host_register_ok = None
+
+
+def host_register_supported() -> bool:
+    """Whether the runtime here can page-lock memory the process already owns
+    (tcsc_hip_host_register; some virtual machines cannot).  Asked once, with
+    one page; a refusal leaves no HIP error behind."""
+    global _host_register_ok
+    if _host_register_ok is None:
+        a = np.zeros(4096, np.uint8)
+        rc = lib().tcsc_hip_host_register(a.ctypes.data, a.nbytes)
+        if rc == TSG_OK:
+            _check(lib().tcsc_hip_host_unregister(a.ctypes.data), "tcsc_hip_host_unregister")
+        elif rc != TSG_ERR_HIP:
+            _check(rc, "tcsc_hip_host_register")
+        _host_register_ok = rc == TSG_OK
+    return _host_register_ok
+
+
 class registered_host:
     """Context manager: page-locks numpy arrays for repeated host-pointer
-    calls (tcsc_hip_host_register), unlocks them on exit."""
+    calls (tcsc_hip_host_register), unlocks them on exit.  Raises TSGError
+    where host_register_supported() is False."""
 
     def __init__(self, *arrays):
         self.arrays = [a for a in arrays if a is not None and a.size]

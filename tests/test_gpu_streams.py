@@ -143,6 +143,8 @@ def test_host_pointer_pipeline_chunks(tsg, oracle_mod, chunks):
 def test_host_pointer_registered_buffers(tsg, oracle_mod):
     """Caller buffers page-locked once (tcsc_hip_host_register) for repeated
     host-pointer calls: same bits as pageable buffers, pipelined or not."""
+    if not tsg.host_register_supported():
+        pytest.skip("hipHostRegister is not supported here")
     O = oracle_mod
     K, N, M = 900, 1100, 700
     t = O.tcsc_encode(O.gen_ternary(K, N, 4, 28))
@@ -158,6 +160,35 @@ def test_host_pointer_registered_buffers(tsg, oracle_mod):
             h(X, bn, Y, M, N, K)
             assert np.array_equal(Y.view(np.uint32), ref)
     h(X, bn, Y, M, N, K)  # unregistered again
+    assert np.array_equal(Y.view(np.uint32), ref)
+    h.close()
+
+
+def test_host_register_refusal_leaves_no_error(tsg, oracle_mod):
+    """Asking for a page-locked caller buffer leaves no HIP error behind,
+    whether the machine grants it or not: where it does not, registered_host
+    raises TSGError, and the device and host-pointer calls that follow on the
+    same thread run and stay bit-exact with the buffers pageable."""
+    import torch
+    O = oracle_mod
+    K, N, M = 300, 200, 70
+    t = O.tcsc_encode(O.gen_ternary(K, N, 4, 30))
+    h = tsg.TCSCDevice(*t.arrays, K, N)
+    X = O.init_x_frac(M, K, 31)
+    bn = np.linspace(-1, 1, N).astype(np.float32)
+    Y = np.empty((M, N), np.float32)
+    ref = O.base_tcsc(X, t, bn).view(np.uint32)
+    if tsg.host_register_supported():
+        with tsg.registered_host(X, Y):
+            pass
+    else:
+        with pytest.raises(tsg.TSGError, match="hipHostRegister"):
+            with tsg.registered_host(X, Y):
+                pass
+    Yd = h.gemm_torch(torch.from_numpy(X).cuda(), torch.from_numpy(bn).cuda())
+    torch.cuda.synchronize()
+    assert np.array_equal(_bits(Yd), ref)
+    h(X, bn, Y, M, N, K)
     assert np.array_equal(Y.view(np.uint32), ref)
     h.close()
 
