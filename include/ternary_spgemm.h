@@ -199,8 +199,9 @@ int tcsc_hip_gemm_prelu_dev_ld(tsg_tcsc *h, const float *dX, const float *db, co
  * call uses the work buffer at every M that runs an image;
  * tcsc_hip_reserve(h, max_M) sizes it for that.  The isolation paragraph above
  * holds with [dX, dX + M*K) counted in elements of the type.  The kernel and
- * image an M picks do not depend on the type.  Extension: no reference
- * counterpart. */
+ * image an M picks do not depend on the type, except that an int8 X may run the
+ * integer matrix-core kernel (tcsc_hip_set_i8_mfma below: the same bytes, read
+ * in place).  Extension: no reference counterpart. */
 enum tsg_xtype { TSG_X_F32 = 0, TSG_X_F16 = 1, TSG_X_BF16 = 2, TSG_X_I8 = 3 };
 
 int tcsc_hip_gemm_dev_x(tsg_tcsc *h, const void *dX, int xtype, const float *db, float *dY,
@@ -520,6 +521,36 @@ int tsg_gemm_ex_check(const tsg_gemm_ex *d, int M, int N, int K);
  * compiles (graph capture).  It covers the host-pointer pipeline's M chunks
  * too (each chunk is a call with fewer rows). */
 int tcsc_hip_reserve(tsg_tcsc *h, int max_M);
+
+/* The integer matrix-core kernel (tsg_i8mfma_kernel) for calls
+ * whose activations are int8 after the input stage: _dev_x / _dev_xy /
+ * _dev_scaled with TSG_X_I8, _dev_actquant and _dev_normquant with any xtype,
+ * their PReLU twins, and tcsc_hip_gemm_dev_ex in every in_mode.  Such a call on
+ * an eligible handle -- plain TCSC (CSC+packed registration included) with
+ * K <= 131072 -- can run W dense at 2 bits per entry through
+ * v_mfma_i32_32x32x32_i8 with int32 accumulators instead of the fp32 add
+ * streams.  Same bytes: the activations are integers of magnitude <= 128, so
+ * every partial sum of a chain is an integer of magnitude <= 128 K <= 2^24,
+ * exact in fp32; the chain is the integer dot product, and everything after
+ * it -- scales, + b, PReLU, the fused epilogue, the one rounding to the Y type,
+ * the written-range guarantee, drow_scale_out -- is the same code.  Any M >= 1,
+ * any N, ytype, ldY.  BlockedTCSC handles, K > 131072 and calls with an fp32,
+ * fp16 or bf16 X that is not quantised run as before, whatever the mode.
+ * mode: 0 = automatic (default): the calls it was measured to win, M >= 64
+ * on a W at least a quarter nonzero and M >= 512 on one at least a sixteenth
+ * nonzero; 1 = never; 2 = every eligible call; anything else
+ * TSG_ERR_ARG.  tcsc_hip_call_i8_mfma: 1 if an int8-activation call with M
+ * rows runs the kernel under the handle's current mode, else 0
+ * (tcsc_hip_call_kernel keeps describing the fp32 call).  The image (K x N / 4
+ * bytes, padded to 64 x 128) is built and uploaded on the first such call;
+ * tcsc_hip_reserve(h, max_M) does it ahead when the mode is not 1 and some
+ * M <= max_M would run the kernel, and sizes the quantising calls' int8
+ * scratch (max_M x K bytes).  During stream capture a call whose image or
+ * scratch is not ready is TSG_ERR_ARG naming tcsc_hip_reserve.  An int8 X is
+ * read in place: one launch, no work buffer.  Extension: no reference
+ * counterpart. */
+int tcsc_hip_set_i8_mfma(tsg_tcsc *h, int mode);
+int tcsc_hip_call_i8_mfma(const tsg_tcsc *h, int M);
 
 /* ---- introspection ------------------------------------------------------- */
 typedef struct tsg_info {

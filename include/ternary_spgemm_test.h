@@ -139,6 +139,21 @@ int tsg_ell_build(const int32_t *col_start_pos, const int32_t *col_start_neg, co
                   int64_t ent_cap, int64_t *ent_len, uint32_t *tab, int64_t tab_cap, int64_t *tab_len, int32_t *C,
                   int32_t *nch, int32_t *xb);
 
+/* The integer matrix-core kernel's image (tcsc_hip_set_i8_mfma; tsg_internal.h
+ * I8Geom) of a plain TCSC (B = 0): W dense at 2 bits per entry (+1 = 0, -1 =
+ * 2, zero = 3), zero-padded to geom[0] = Kp rows and geom[1] = Np columns;
+ * geom[2..5] = the workgroup tile's rows and columns, the columns of a wave
+ * tile and the k-step (128, 128, 64, 64).  Fragment order: per (wave tile ct,
+ * k-step ks) 64 lanes x 4 dwords; W[k][n] is in dword
+ *   (((n / 64) * (Kp / 64) + k / 64) * 64 + 32 * (k % 32 / 16) + n % 32) * 4
+ *     + 2 * (n % 64 / 32) + k % 64 / 32
+ * at bits [s, s + 2), s = 8 * (k % 4) + 2 * (k % 16 / 4).  A handle that is
+ * not eligible (B > 0, K > 131072) is TSG_ERR_RANGE.  Host only; a NULL img
+ * queries the length (in uint32) and the geometry. */
+int tsg_i8_build(const int32_t *col_start_pos, const int32_t *col_start_neg, const int32_t *row_index_pos,
+                 const int32_t *row_index_neg, int K, int N, int B, uint32_t *img, int64_t img_cap, int64_t *img_len,
+                 int32_t *geom);
+
 /* The rx kernel's block stream (tsg_tcsc_rx_kernel, the path of a W too large
  * for one compiled image; csrc/tsg_internal.h RxImage): per (256-column tile,
  * wave) the first dword of that wave's stream in wstart, the stream's blocks

@@ -76,6 +76,9 @@ struct tsg_tcsc {
         bool ready = false;
     };
     EllVariant ell[tsg::kEllVariants];
+    // integer matrix-core kernel (tsg_i8mfma.hip): the packed dense image, built
+    // on the first call (or tcsc_hip_reserve) that runs it
+    uint32_t *d_i8 = nullptr;
     std::vector<int32_t> csp, csn, rip, rin;  // host TCSC (getVectorRepresentation)
     uint32_t *d_seg = nullptr, *d_ent = nullptr;
     float *d_work = nullptr;              // X^T [Kp][Mp]
@@ -455,13 +458,14 @@ struct Call {
 // Before a call stages its X^T: the work buffer holds it (ensure_work), and
 // X^T of the previous call may still be read by its kernel on another
 // stream: this call's staging waits for it (same stream: stream order)
-int work_begin(tsg_tcsc *h, const CallPlan &p, const Call &c)
+int work_begin(tsg_tcsc *h, const CallPlan &p, const Call &c, bool q8)
 {
     const int M = c.in.M;
-    // (a walk has no X^T: it comes here for the actquant scratch alone)
-    int rc = p.is_ell() ? TSG_OK : ensure_work(h, M, p.tile_m, p.chunk, c.capturing);
+    // (q8: a kernel that reads X in place -- a walk, the integer matrix-core
+    // kernel -- has no X^T: it comes here for the actquant scratch alone)
+    int rc = q8 ? TSG_OK : ensure_work(h, M, p.tile_m, p.chunk, c.capturing);
     if (!rc && c.quant)
-        rc = ensure_aq(h, M, p.is_ell() ? std::max<size_t>((size_t)M * h->plan.K, 16) : 0, c.capturing);
+        rc = ensure_aq(h, M, q8 ? std::max<size_t>((size_t)M * h->plan.K, 16) : 0, c.capturing);
     if (rc) return rc;
     if (!c.capturing && h->work_used && h->work_stream != c.s()) HIP_TRY(hipStreamWaitEvent(c.s(), h->work_ev, 0));
     return TSG_OK;
@@ -488,7 +492,7 @@ int work_end(tsg_tcsc *h, const Call &c)
 // fills them (deq also to the caller), for a walk (q8) also the int8 q
 int stage_begin(tsg_tcsc *h, const CallPlan &p, Call &c, bool q8)
 {
-    const int rc = work_begin(h, p, c);
+    const int rc = work_begin(h, p, c, q8);
     if (rc || !c.quant) return rc;
     float *const deq = h->d_aq + h->aq_rows;
     c.in.inv = h->d_aq;
@@ -526,6 +530,62 @@ int run_ell(tsg_tcsc *h, const CallPlan &p, Call &c)
                                                : tsg::launch_tcsc_ell(p.ell, c.in.X, c.in.xtype, e, c.out);
     if (lrc != 0)
         return fail(TSG_ERR_HIP, std::string("small-M kernel launch: ") + hipGetErrorString(hipGetLastError()));
+    rc = timing_end(h, slot, c.s());
+    return rc || !c.quant ? rc : work_end(h, c);
+}
+
+// Builds and uploads the integer matrix-core kernel's image (tsg_internal.h
+// I8Geom).  Caller holds h->mu.
+int ensure_i8(tsg_tcsc *h)
+{
+    if (h->d_i8) return TSG_OK;
+    const tsg::I8Geom g = tsg::i8_geom(h->plan.K, h->plan.N);
+    std::vector<uint32_t> img((size_t)g.words());
+    tsg::build_i8_image(h->csp.data(), h->csn.data(), h->rip.empty() ? nullptr : h->rip.data(),
+                        h->rin.empty() ? nullptr : h->rin.data(), h->plan.K, h->plan.N, g, img.data());
+    DeviceGuard dg(h->device);
+    // the handle owns the image only once the upload succeeded (a failed
+    // attempt leaves nothing behind)
+    uint32_t *d = nullptr;
+    if (hipMalloc(&d, std::max<size_t>(img.size() * 4, 16)) != hipSuccess)
+        return fail(TSG_ERR_NOMEM, "hipMalloc of the int8 matrix-core image failed");
+    if (!img.empty() && hipMemcpy(d, img.data(), img.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(d);
+        return fail(TSG_ERR_HIP, "upload of the int8 matrix-core image failed");
+    }
+    h->d_i8 = d;
+    return TSG_OK;
+}
+
+// int8 activations on the integer matrix cores (tsg_plan.h call_i8_mfma): an
+// int8 X is read in place -- no work buffer, one launch; a quantising call's
+// row pass writes q as int8 into the scratch and the kernel runs on it as an
+// int8-X call scaled by the scratch's deq, as the walks do
+int run_i8(tsg_tcsc *h, Call &c)
+{
+    const int M = c.in.M;
+    // a captured call that cannot run is refused before anything is enqueued:
+    // the scratch first (the message of the other quantising paths), then the image
+    if (c.capturing && c.quant)
+        if (const int rq = ensure_aq(h, M, std::max<size_t>((size_t)M * h->plan.K, 16), true)) return rq;
+    if (!h->d_i8 && c.capturing)
+        return fail(TSG_ERR_ARG, "M=" + std::to_string(M) + " runs the int8 matrix-core kernel, whose image is not "
+                                 "built yet; call tcsc_hip_reserve before capturing");
+    if (((int64_t)M + tsg::kI8TileM - 1) / tsg::kI8TileM * (((int64_t)h->plan.N + tsg::kI8TileN - 1) / tsg::kI8TileN) >=
+        (1ll << 31) / 256)
+        return fail(TSG_ERR_ARG, "M=" + std::to_string(M) + " is too large for one launch; split the rows");
+    int rc = ensure_i8(h);
+    if (rc) return rc;
+    if (c.quant) {
+        rc = stage_begin(h, CallPlan{}, c, true);
+        if (rc) return rc;
+        c.in.X = h->d_aq8, c.in.xtype = tsg::kXI8;
+    }
+    int slot;
+    rc = timing_begin(h, c.capturing, c.s(), slot);
+    if (rc) return rc;
+    if (tsg::launch_tcsc_i8mfma(static_cast<const int8_t *>(c.in.X), h->d_i8, h->plan.K, c.out) != 0)
+        return fail(TSG_ERR_HIP, std::string("int8 matrix-core kernel launch: ") + hipGetErrorString(hipGetLastError()));
     rc = timing_end(h, slot, c.s());
     return rc || !c.quant ? rc : work_end(h, c);
 }
@@ -674,6 +734,7 @@ int run_dev(tsg_tcsc *h, Call c)
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     HIP_TRY(hipStreamIsCapturing(c.s(), &cap));
     c.capturing = cap != hipStreamCaptureStatusNone;
+    if (tsg::call_i8_mfma(h->plan, M, c.quant || c.in.xtype == tsg::kXI8)) return run_i8(h, c);
     CallPlan p = tsg::plan_call(h->plan, M);
     if (p.is_ell()) return run_ell(h, p, c);
     if (!p.is_jit()) return run_rx(h, p, c);
@@ -888,7 +949,7 @@ void free_handle(tsg_tcsc *h)
     if (h->work_ev) (void)hipEventDestroy(h->work_ev);
     for (void *p : {(void *)h->d_seg, (void *)h->d_ent, (void *)h->d_work, (void *)h->d_x,
                     (void *)h->d_b, (void *)h->d_y, (void *)h->d_alpha, (void *)h->d_status, (void *)h->d_aq,
-                    (void *)h->d_aq8})
+                    (void *)h->d_aq8, (void *)h->d_i8})
         if (p) (void)hipFree(p);
     for (auto *vs : {&h->jv[0], &h->jv64[0], &h->jv64h[0]})
         for (size_t i = 0; i < (vs == &h->jv[0] ? std::size(h->jv) : vs == &h->jv64[0] ? std::size(h->jv64)
@@ -1183,6 +1244,14 @@ extern "C" int tcsc_hip_reserve(tsg_tcsc *h, int max_M)
         if (tsg::plan_call(h->plan, m).is_ell()) walk_m = m;
     int rc = ensure_aq(h, max_M, walk_m ? std::max<size_t>((size_t)walk_m * h->plan.K, 16) : 0, false);
     if (rc) return rc;
+    // the integer matrix-core kernel, when some M <= max_M runs it (its rule is
+    // monotone in M: the largest decides): the image, and the int8 q of a
+    // quantising call with max_M rows
+    if (tsg::call_i8_mfma(h->plan, std::max(max_M, 1), true)) {
+        rc = ensure_i8(h);
+        if (!rc) rc = ensure_aq(h, max_M, std::max<size_t>((size_t)std::max(max_M, 1) * h->plan.K, 16), false);
+        if (rc) return rc;
+    }
     if (!h->plan.jit) return ensure_work(h, max_M, tsg::kRxTileM, tsg::kRxChunk, false);
     rc = ensure_work(h, max_M, tsg::kJitTileM, tsg::kJitChunk, false);
     // the 64-row image's k-quad X^T (same bytes or fewer)
@@ -1347,6 +1416,23 @@ extern "C" int tcsc_hip_set_small_m(tsg_tcsc *h, int mode)
     std::lock_guard<std::mutex> lk(h->mu);
     h->plan.small_m = mode;
     return TSG_OK;
+}
+
+extern "C" int tcsc_hip_set_i8_mfma(tsg_tcsc *h, int mode)
+{
+    if (!h) return fail(TSG_ERR_ARG, "null handle");
+    if (mode < 0 || mode > 2)
+        return fail(TSG_ERR_ARG, "tcsc_hip_set_i8_mfma: expected 0 (auto), 1 (never) or 2 (every eligible call)");
+    std::lock_guard<std::mutex> lk(h->mu);
+    h->plan.i8_mode = mode;
+    return TSG_OK;
+}
+
+extern "C" int tcsc_hip_call_i8_mfma(const tsg_tcsc *h, int M)
+{
+    if (!h || M <= 0) return 0;
+    std::lock_guard<std::mutex> lk(h->mu);
+    return tsg::call_i8_mfma(h->plan, M, true) ? 1 : 0;
 }
 
 // what the planner reads of an unpinned plain-TCSC handle with K, N and nnz nonzeros

@@ -10,6 +10,7 @@
 
 #include "../../include/ternary_spgemm_test.h"
 #include "tsg_internal.h"
+#include "tsg_plan.h"
 
 namespace tsg {
 
@@ -571,5 +572,52 @@ extern "C" int tsg_rx_build(const int32_t *csp, const int32_t *csn, const int32_
     }
     if (wstart) std::memcpy(wstart, img.wstart.data(), img.wstart.size() * 4);
     if (ent) std::memcpy(ent, img.ent.data(), img.ent.size() * 4);
+    return TSG_OK;
+}
+
+// The integer matrix-core kernel's image (tsg_internal.h I8Geom): every entry
+// starts as the zero code, then one pass over the nonzeros writes theirs.
+void tsg::build_i8_image(const int32_t *csp, const int32_t *csn, const int32_t *rip, const int32_t *rin, int K, int N,
+                         const I8Geom &g, uint32_t *img)
+{
+    (void)K;
+    std::fill(img, img + g.words(), kI8Zero * 0x55555555u);
+    for (int n = 0; n < N; n++) {
+        for (int32_t i = csp[n]; i < csp[n + 1]; i++) {
+            uint32_t &w = img[g.word(rip[i], n)];
+            w = (w & ~(3u << I8Geom::shift(rip[i]))) | (kI8Pos << I8Geom::shift(rip[i]));
+        }
+        for (int32_t i = csn[n]; i < csn[n + 1]; i++) {
+            uint32_t &w = img[g.word(rin[i], n)];
+            w = (w & ~(3u << I8Geom::shift(rin[i]))) | (kI8Neg << I8Geom::shift(rin[i]));
+        }
+    }
+}
+
+// Host-only view of that image (tests unpack it on the CPU).  NULL img queries
+// the length; an ineligible W (tsg_plan.h i8_eligible) is TSG_ERR_RANGE.
+extern "C" int tsg_i8_build(const int32_t *csp, const int32_t *csn, const int32_t *rip, const int32_t *rin, int K,
+                            int N, int B, uint32_t *img, int64_t img_cap, int64_t *img_len, int32_t *geom)
+{
+    tsg::PlanInput in;
+    in.K = K, in.N = N, in.B = B;
+    if (K < 0 || N < 0 || !tsg::i8_eligible(in)) {
+        g_tsg_host_err = "tsg_i8_build: the int8 matrix-core image needs a plain TCSC with K <= " +
+                         std::to_string(tsg::kI8MaxK);
+        return K < 0 || N < 0 ? TSG_ERR_ARG : TSG_ERR_RANGE;
+    }
+    const tsg::I8Geom g = tsg::i8_geom(K, N);
+    if (img_len) *img_len = g.words();
+    if (geom) {
+        const int32_t v[6] = {g.Kp, g.Np, tsg::kI8TileM, tsg::kI8TileN, tsg::kI8WaveN, tsg::kI8KStep};
+        std::memcpy(geom, v, sizeof v);
+    }
+    if (!img) return TSG_OK;
+    const std::string e = tsg::validate_tcsc(csp, csn, rip, rin, K, N);
+    if (!e.empty() || img_cap < g.words()) {
+        g_tsg_host_err = e.empty() ? "tsg_i8_build: buffer too small" : "tsg_i8_build: " + e;
+        return TSG_ERR_ARG;
+    }
+    tsg::build_i8_image(csp, csn, rip, rin, K, N, g, img);
     return TSG_OK;
 }

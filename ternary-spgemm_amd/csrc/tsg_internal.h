@@ -388,6 +388,56 @@ constexpr size_t kLdsBytes = 160 * 1024;
 size_t ell_pc_lds_bytes(int variant, int C);
 int launch_tcsc_ell_pc(int variant, const void *X, int xtype, const EllDev &e, const YOut &o);
 
+// ---------------------------------------------------------------------------
+// "i8mfma" kernel (tsg_i8mfma_kernel, tsg_i8mfma.hip): the int8-activation
+// calls on the integer matrix cores, dense over W.  A workgroup of 4 waves owns
+// 128 rows x 128 columns, a wave 64 x 64 as 2 x 2 accumulator tiles of
+// v_mfma_i32_32x32x32_i8; K goes by in steps of 64 (two matrix instructions
+// deep).  Eligibility and the exactness bound: tsg_plan.h call_i8_mfma.
+//
+// The image: W dense at 2 bits per entry, K padded to the k-step and N to the
+// workgroup tile with zeros, in the order the B fragments are consumed.  Per
+// (64-column wave tile ct, k-step ks) 64 lanes x 4 dwords = 1 KiB, a lane's 16
+// bytes one load: dword f = 2 * c2 + kk is the lane's share of the fragment of
+// column half c2 (32 columns) and k half kk (32 rows) -- the 16 entries
+//   k = 64 ks + 32 kk + 16 (lane / 32) + e,  n = 64 ct + 32 c2 + lane % 32
+// with entry e = 4 d + b (byte b of the fragment's dword d) in bits
+// [8 b + 2 d, 8 b + 2 d + 2).  The A fragments take the same k of a lane
+// (tsg_i8mfma.hip), so the sum over a matrix instruction's 32 k pairs the right
+// bytes whatever order the hardware walks them in.
+// Code: +1 = 0, -1 = 2, zero = 3.  Shifted to bits 2-3 of its byte and masked
+// it is a v_perm_b32 selector -- 0 (byte 0 of a source: 0x01), 8 (the sign of
+// a source byte, set: 0xff), 12 (constant 0x00) -- so a dword of four int8
+// entries costs a shift, a v_and_b32 and a v_perm_b32.
+constexpr int kI8TileM = 128, kI8TileN = 128;   // workgroup tile
+constexpr int kI8WaveN = 64;                    // columns of a wave tile (image granule)
+constexpr int kI8KStep = 64;
+constexpr int kI8MaxK = 131072;                 // 128 * K <= 2^24 (tsg_plan.h)
+constexpr uint32_t kI8Pos = 0, kI8Neg = 2, kI8Zero = 3;
+struct I8Geom {
+    int Kp = 0, Np = 0;                         // K, N padded to kI8KStep, kI8TileN
+    int64_t words() const { return (int64_t)Kp * Np / 16; }
+    // the dword holding W[k][n] and the position of its 2-bit code there
+    int64_t word(int k, int n) const
+    {
+        const int lane = 32 * (k % 32 / 16) + n % 32, f = 2 * (n % kI8WaveN / 32) + k % kI8KStep / 32;
+        return (((int64_t)(n / kI8WaveN) * (Kp / kI8KStep) + k / kI8KStep) * 64 + lane) * 4 + f;
+    }
+    static int shift(int k) { return 8 * (k % 4) + 2 * (k % 16 / 4); }
+};
+inline I8Geom i8_geom(int K, int N)
+{
+    I8Geom g;
+    g.Kp = (K + kI8KStep - 1) / kI8KStep * kI8KStep;
+    g.Np = (N + kI8TileN - 1) / kI8TileN * kI8TileN;
+    return g;
+}
+// img: g.words() dwords; one pass over the nonzeros of a plain TCSC
+void build_i8_image(const int32_t *csp, const int32_t *csn, const int32_t *rip, const int32_t *rin, int K, int N,
+                    const I8Geom &g, uint32_t *img);
+// X: int8 [M][K] row-major (the caller's, or the quantising calls' scratch); img: uploaded
+int launch_tcsc_i8mfma(const int8_t *X, const uint32_t *img, int K, const YOut &o);
+
 // Environment knobs (csrc/tsg_knobs.cpp): A/B studies and tests, none of
 // which changes a result.  knob_check: "" when every set knob has an
 // accepted value, else the first error (registration and the host codegen

@@ -624,6 +624,28 @@ CallPlan plan_call(const PlanInput &in, int M)
     return p;
 }
 
+bool i8_eligible(const PlanInput &in)
+{
+    return in.B == 0 && in.K <= kI8MaxK;
+}
+
+// The automatic rule, from profiles/i8mfma_ab.jsonl (int8 X,
+// bf16 Y, both scales at K = 4096, N = 16384; parent add streams / this kernel,
+// medians in ms).  The kernel's time does not depend on the density -- 0.041 at
+// M = 64, 0.060 at 512, 0.33 at 4096 -- the add streams' does:
+//   density 2/3: 0.098 / 0.410 / 2.873    1/2:  0.085 / 0.326 / 2.146
+//           1/4: 0.064 / 0.188 / 1.253    1/16: 0.037 (the walk) / 0.081 / 0.418
+// So it wins past the parent's spread from M = 64 at a density of 1/4 and up,
+// and from M = 512 at 1/16 and up; at (64, 1/16) the walk wins.  Below M = 64
+// and below 1/16 nothing was measured: never.
+bool call_i8_mfma(const PlanInput &in, int M, bool int8_acts)
+{
+    if (!int8_acts || M < 1 || in.i8_mode == 1 || !i8_eligible(in)) return false;
+    if (in.i8_mode == 2) return true;
+    const int64_t kn = (int64_t)in.K * in.N;
+    return in.nnz > 0 && ((M >= 64 && 4 * in.nnz >= kn) || (M >= 512 && 16 * in.nnz >= kn));
+}
+
 // Chunks of the host-pointer pipeline: one per ~16 MiB of Y (the PCIe leg
 // that binds: Y is the largest transfer), at most kHostChunksMax, each a whole
 // number of 128-row M tiles and at least 256 rows; calls the small-M kernel

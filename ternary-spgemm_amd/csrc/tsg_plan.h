@@ -38,6 +38,7 @@ struct PlanInput {
     // that pick them run the 128-row 64 x 8 image (loaded on that fallback)
     uint32_t bad_variants = 0;
     int jit_nch = 0;            // X^T chunks of the 128-row images (all widths)
+    int i8_mode = 0;            // tcsc_hip_set_i8_mfma: 0 auto, 1 never, 2 every eligible call
 };
 
 enum class Kernel { kRx, kJit128, kJit64, kEll, kEllPc };
@@ -55,6 +56,21 @@ struct CallPlan {
 };
 
 CallPlan plan_call(const PlanInput &in, int M);
+
+// The integer matrix-core kernel (tsg_i8mfma.hip) instead of what plan_call
+// picks.  A handle is eligible when it is plain TCSC with K <= kI8MaxK: the
+// activations are integers of magnitude <= 128, so every partial sum of a chain
+// is an integer of magnitude <= 128 K <= 2^24, which fp32 holds exactly -- the
+// fp32 chain of the other kernels is then the int32 dot product, bit for bit
+// (BlockedTCSC sums block by block, the same value, but its handles hold no
+// plain TCSC to build the image from; past the bound the fp32 chain rounds).
+// A call is eligible when its activations are int8 after the input stage
+// (int8_acts: an int8 X, or an actquant / normquant call).  i8_mode 2 sends
+// every eligible call there, 1 none; 0, the automatic rule, those the kernel
+// was measured to win by more than the add streams' own spread: M >= 64 at a
+// density nnz / (K N) of 1/4 and up, M >= 512 at 1/16 and up.
+bool i8_eligible(const PlanInput &in);
+bool call_i8_mfma(const PlanInput &in, int M, bool int8_acts);
 
 // Logical workgroup ids of a weight-compiled call: M tiles x column tiles
 // (cols = stream width x streams per workgroup)

@@ -56,6 +56,7 @@ EXPORTED_SYMBOLS = (
     "tcsc_hip_gemm_dev_actquant", "tcsc_hip_gemm_prelu_dev_actquant",
     "tcsc_hip_gemm_dev_normquant", "tcsc_hip_gemm_prelu_dev_normquant",
     "tcsc_hip_gemm_dev_ex", "tsg_gemm_ex_check", "tsg_call_grid", "tcsc_hip_last_launch",
+    "tcsc_hip_set_i8_mfma", "tcsc_hip_call_i8_mfma", "tsg_i8_build",
 )
 
 # enum tsg_xtype (include/ternary_spgemm.h): element type of X on the _x calls
@@ -215,6 +216,10 @@ def lib() -> C.CDLL:
     L.tsg_rx_build.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, vp, C.c_int64, C.POINTER(C.c_int64), vp, C.c_int64,
                                C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
     L.tsg_jit_tile_map.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.tcsc_hip_set_i8_mfma.argtypes = [H, C.c_int]
+    L.tcsc_hip_call_i8_mfma.argtypes = [H, C.c_int]
+    L.tsg_i8_build.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int64, C.POINTER(C.c_int64),
+                               C.POINTER(C.c_int32)]
     L.tcsc_hip_jit_width.argtypes = [H, C.c_int]
     L.tcsc_hip_jit_waves.argtypes = [H, C.c_int]
     L.tcsc_hip_set_jit_width.argtypes = [H, C.c_int]
@@ -433,6 +438,21 @@ def ell_build(csp, csn, rip, rin, K: int, N: int, Cmax: int, MT: int, copies: in
            "tsg_ell_build")
     out = (ent.view(np.uint16), tab.reshape(-1, 2), c.value, nch.value)
     return out + (xb.value,) if with_xb else out
+
+
+def i8_build(csp, csn, rip, rin, K: int, N: int, B: int = 0):
+    """Host view of the integer matrix-core kernel's image (tsg_i8_build,
+    include/ternary_spgemm_test.h): (img uint32[], geom = (Kp, Np, tile rows,
+    tile columns, wave-tile columns, k-step)).  Raises TSGError (TSG_ERR_RANGE)
+    for a W the kernel is not eligible for: B > 0 or K > 131072."""
+    csp, csn, rip, rin = _i32(csp), _i32(csn), _i32(rip), _i32(rin)
+    n, geom = C.c_int64(), (C.c_int32 * 6)()
+    L = lib()
+    _check(L.tsg_i8_build(_ptr(csp), _ptr(csn), _ptr(rip), _ptr(rin), K, N, B, None, 0, C.byref(n), geom), "tsg_i8_build")
+    img = np.empty(n.value, np.uint32)
+    _check(L.tsg_i8_build(_ptr(csp), _ptr(csn), _ptr(rip), _ptr(rin), K, N, B, _ptr(img), n.value, C.byref(n), geom),
+           "tsg_i8_build")
+    return img, tuple(geom)
 
 
 def rx_build(csp, csn, rip, rin, K: int, N: int):
@@ -1190,6 +1210,16 @@ class TCSCDevice:
         """Small-M kernel: 0 = automatic (default), 1 = never, 2 = every call,
         3 = every call without the producer/consumer walk (M <= 4)."""
         _check(lib().tcsc_hip_set_small_m(self._h, mode), "tcsc_hip_set_small_m")
+
+    def set_i8_mfma(self, mode: int) -> None:
+        """Integer matrix-core kernel for the int8-activation calls: 0 =
+        automatic (default), 1 = never, 2 = every eligible call."""
+        _check(lib().tcsc_hip_set_i8_mfma(self._h, mode), "tcsc_hip_set_i8_mfma")
+
+    def call_i8_mfma(self, M: int) -> int:
+        """1 if an int8-activation call with M rows runs tsg_i8mfma_kernel
+        under the handle's current mode, else 0."""
+        return int(lib().tcsc_hip_call_i8_mfma(self._h, M))
 
     def set_host_chunks(self, chunks: int) -> None:
         """Host-pointer calls: 0 = automatic M-chunk pipeline (default), n =
