@@ -547,10 +547,23 @@ int tcsc_hip_reserve(tsg_tcsc *h, int max_M);
  * M <= max_M would run the kernel, and sizes the quantising calls' int8
  * scratch (max_M x K bytes).  During stream capture a call whose image or
  * scratch is not ready is TSG_ERR_ARG naming tcsc_hip_reserve.  An int8 X is
- * read in place: one launch, no work buffer.  Extension: no reference
- * counterpart. */
+ * read in place: one launch, no work buffer.
+ * Decode shapes: an eligible call with 1 <= M <= 32 that runs on the matrix
+ * cores runs tsg_i8gemv_kernel instead of the 128 x 128 tiles: the same image,
+ * one workgroup per 32 or 64 columns, K split across its waves and the int32
+ * partial sums added in LDS -- any order gives the same integer, so the same
+ * bytes again.  tcsc_hip_call_i8_kernel: which integer kernel such a call
+ * with M rows runs under the current mode, 0 none, 1 tsg_i8mfma_kernel, 2
+ * tsg_i8gemv_kernel (tcsc_hip_call_i8_mfma is "1 or 2").  Mode 2 sends every
+ * eligible call with M <= 32 there; mode 0 those it was measured to win
+ * (2-10 x the walks at K = 4096, N = 4096 and 16384): K >= 4096
+ * and N >= 4096, and either a W at least a quarter nonzero, or one at least a
+ * sixteenth nonzero with M >= 8.  33 <= M <= 63 runs as before.
+ * tcsc_hip_reserve also covers the M <= 32 calls of a larger max_M.
+ * Extension: no reference counterpart. */
 int tcsc_hip_set_i8_mfma(tsg_tcsc *h, int mode);
 int tcsc_hip_call_i8_mfma(const tsg_tcsc *h, int M);
+int tcsc_hip_call_i8_kernel(const tsg_tcsc *h, int M);
 
 /* ---- introspection ------------------------------------------------------- */
 typedef struct tsg_info {

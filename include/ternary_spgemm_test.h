@@ -154,6 +154,16 @@ int tsg_i8_build(const int32_t *col_start_pos, const int32_t *col_start_neg, con
                  const int32_t *row_index_neg, int K, int N, int B, uint32_t *img, int64_t img_cap, int64_t *img_len,
                  int32_t *geom);
 
+/* The M <= 32 integer matrix-core kernel (tsg_i8gemv_kernel).
+ * tcsc_hip_set_i8_small: 0 = the rule of tcsc_hip_set_i8_mfma (default), 1 =
+ * never: an eligible call with M <= 32 runs what it ran before that kernel
+ * existed (under mode 2 the 128 x 128 tiles) -- old and new in one process for
+ * tests and A/B; anything else TSG_ERR_ARG.  Same results bit for bit.
+ * tsg_i8gemv_pick (host only): the launch of a call on a K x N handle, the
+ * columns of a workgroup's tile (32 or 64) and its waves (1, 2, 4, 8 or 16). */
+int tcsc_hip_set_i8_small(tsg_tcsc *h, int mode);
+int tsg_i8gemv_pick(int K, int N, int *tile_cols, int *waves);
+
 /* The rx kernel's block stream (tsg_tcsc_rx_kernel, the path of a W too large
  * for one compiled image; csrc/tsg_internal.h RxImage): per (256-column tile,
  * wave) the first dword of that wave's stream in wstart, the stream's blocks

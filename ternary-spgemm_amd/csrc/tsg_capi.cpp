@@ -560,8 +560,10 @@ int ensure_i8(tsg_tcsc *h)
 // int8 activations on the integer matrix cores (tsg_plan.h call_i8_mfma): an
 // int8 X is read in place -- no work buffer, one launch; a quantising call's
 // row pass writes q as int8 into the scratch and the kernel runs on it as an
-// int8-X call scaled by the scratch's deq, as the walks do
-int run_i8(tsg_tcsc *h, Call &c)
+// int8-X call scaled by the scratch's deq, as the walks do.  `kernel`
+// (tsg_plan.h call_i8_kernel): 1 the 128 x 128 tiles, 2 the M <= 32 split-K
+// kernel; both read the one image.
+int run_i8(tsg_tcsc *h, Call &c, int kernel)
 {
     const int M = c.in.M;
     // a captured call that cannot run is refused before anything is enqueued:
@@ -584,7 +586,9 @@ int run_i8(tsg_tcsc *h, Call &c)
     int slot;
     rc = timing_begin(h, c.capturing, c.s(), slot);
     if (rc) return rc;
-    if (tsg::launch_tcsc_i8mfma(static_cast<const int8_t *>(c.in.X), h->d_i8, h->plan.K, c.out) != 0)
+    const int8_t *X8 = static_cast<const int8_t *>(c.in.X);
+    if ((kernel == 2 ? tsg::launch_tcsc_i8gemv(X8, h->d_i8, h->plan.K, c.out)
+                     : tsg::launch_tcsc_i8mfma(X8, h->d_i8, h->plan.K, c.out)) != 0)
         return fail(TSG_ERR_HIP, std::string("int8 matrix-core kernel launch: ") + hipGetErrorString(hipGetLastError()));
     rc = timing_end(h, slot, c.s());
     return rc || !c.quant ? rc : work_end(h, c);
@@ -734,7 +738,7 @@ int run_dev(tsg_tcsc *h, Call c)
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     HIP_TRY(hipStreamIsCapturing(c.s(), &cap));
     c.capturing = cap != hipStreamCaptureStatusNone;
-    if (tsg::call_i8_mfma(h->plan, M, c.quant || c.in.xtype == tsg::kXI8)) return run_i8(h, c);
+    if (const int i8 = tsg::call_i8_kernel(h->plan, M, c.quant || c.in.xtype == tsg::kXI8)) return run_i8(h, c, i8);
     CallPlan p = tsg::plan_call(h->plan, M);
     if (p.is_ell()) return run_ell(h, p, c);
     if (!p.is_jit()) return run_rx(h, p, c);
@@ -1244,10 +1248,12 @@ extern "C" int tcsc_hip_reserve(tsg_tcsc *h, int max_M)
         if (tsg::plan_call(h->plan, m).is_ell()) walk_m = m;
     int rc = ensure_aq(h, max_M, walk_m ? std::max<size_t>((size_t)walk_m * h->plan.K, 16) : 0, false);
     if (rc) return rc;
-    // the integer matrix-core kernel, when some M <= max_M runs it (its rule is
-    // monotone in M: the largest decides): the image, and the int8 q of a
-    // quantising call with max_M rows
-    if (tsg::call_i8_mfma(h->plan, std::max(max_M, 1), true)) {
+    // the integer matrix-core kernels, when some M <= max_M runs one: the
+    // image, and the int8 q of a quantising call with max_M rows.  The tile
+    // kernel's rule is monotone in M, the largest decides; the M <= 32
+    // kernel's rule can hold at 32 and not from 33 to 63, so that M is asked too
+    if (tsg::call_i8_mfma(h->plan, std::max(max_M, 1), true) ||
+        tsg::call_i8_mfma(h->plan, std::max(std::min(max_M, tsg::kI8GemvMaxM), 1), true)) {
         rc = ensure_i8(h);
         if (!rc) rc = ensure_aq(h, max_M, std::max<size_t>((size_t)std::max(max_M, 1) * h->plan.K, 16), false);
         if (rc) return rc;
@@ -1433,6 +1439,31 @@ extern "C" int tcsc_hip_call_i8_mfma(const tsg_tcsc *h, int M)
     if (!h || M <= 0) return 0;
     std::lock_guard<std::mutex> lk(h->mu);
     return tsg::call_i8_mfma(h->plan, M, true) ? 1 : 0;
+}
+
+extern "C" int tcsc_hip_call_i8_kernel(const tsg_tcsc *h, int M)
+{
+    if (!h || M <= 0) return 0;
+    std::lock_guard<std::mutex> lk(h->mu);
+    return tsg::call_i8_kernel(h->plan, M, true);
+}
+
+extern "C" int tcsc_hip_set_i8_small(tsg_tcsc *h, int mode)
+{
+    if (!h) return fail(TSG_ERR_ARG, "null handle");
+    if (mode < 0 || mode > 1) return fail(TSG_ERR_ARG, "tcsc_hip_set_i8_small: expected 0 (auto) or 1 (never)");
+    std::lock_guard<std::mutex> lk(h->mu);
+    h->plan.i8_small = mode;
+    return TSG_OK;
+}
+
+extern "C" int tsg_i8gemv_pick(int K, int N, int *tile_cols, int *waves)
+{
+    if (K < 0 || N < 0) return fail(TSG_ERR_ARG, "tsg_i8gemv_pick: K < 0 or N < 0");
+    const tsg::I8GemvPick p = tsg::i8gemv_pick(K, N);
+    if (tile_cols) *tile_cols = p.tn;
+    if (waves) *waves = p.S;
+    return TSG_OK;
 }
 
 // what the planner reads of an unpinned plain-TCSC handle with K, N and nnz nonzeros

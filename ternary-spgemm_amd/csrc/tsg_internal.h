@@ -438,6 +438,34 @@ void build_i8_image(const int32_t *csp, const int32_t *csn, const int32_t *rip, 
 // X: int8 [M][K] row-major (the caller's, or the quantising calls' scratch); img: uploaded
 int launch_tcsc_i8mfma(const int8_t *X, const uint32_t *img, int K, const YOut &o);
 
+// "i8gemv" kernel (tsg_i8gemv_kernel, tsg_i8gemv.hip): the same calls with
+// 1 <= M <= kI8GemvMaxM rows, over the same image.  One workgroup per column
+// tile of tn = 32 or 64 columns (half a granule of the image, or one), its S
+// waves splitting the k-steps, wave w taking w, w + S, ...; the partial sums
+// meet in LDS, S x tn / 2 x 256 bytes.  i8gemv_pick, the launcher's choice:
+// tn = 64 only where N / 64 workgroups still give every compute unit of the
+// MI355X one, else 32; S the largest of 1, 2, 4, 8, 16 that is at most the
+// k-steps and whose LDS stays within kI8GemvLds, so that two workgroups fit a
+// CU's 160 KiB (and a launch needs no opt-in above 64 KiB): 8 waves at 64
+// columns, 16 at 32.
+constexpr int kI8GemvMaxM = 32;
+constexpr int kI8GemvCUs = 256;
+constexpr int kI8GemvLds = 64 * 1024;
+constexpr int kI8GemvWaves64 = kI8GemvLds / (32 * 256), kI8GemvWaves32 = kI8GemvLds / (16 * 256);
+struct I8GemvPick {
+    int tn, S;
+};
+inline I8GemvPick i8gemv_pick(int K, int N)
+{
+    I8GemvPick p;
+    p.tn = N / kI8WaveN >= kI8GemvCUs ? 64 : 32;
+    const int nks = (K + kI8KStep - 1) / kI8KStep, cap = p.tn == 64 ? kI8GemvWaves64 : kI8GemvWaves32;
+    for (p.S = 1; 2 * p.S <= cap && 2 * p.S <= nks;) p.S *= 2;
+    return p;
+}
+// X: int8 [M][K] row-major, M <= kI8GemvMaxM; img: the i8mfma image, uploaded
+int launch_tcsc_i8gemv(const int8_t *X, const uint32_t *img, int K, const YOut &o);
+
 // Environment knobs (csrc/tsg_knobs.cpp): A/B studies and tests, none of
 // which changes a result.  knob_check: "" when every set knob has an
 // accepted value, else the first error (registration and the host codegen

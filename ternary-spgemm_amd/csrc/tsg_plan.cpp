@@ -638,12 +638,35 @@ bool i8_eligible(const PlanInput &in)
 // So it wins past the parent's spread from M = 64 at a density of 1/4 and up,
 // and from M = 512 at 1/16 and up; at (64, 1/16) the walk wins.  Below M = 64
 // and below 1/16 nothing was measured: never.
+//
+// M <= 32 (tsg_i8gemv_kernel), from profiles/i8gemv_ab.jsonl (DESIGN.md 4.7:
+// the same call at M = 1, 8, 16, 32, K = 4096, N = 16384 and 4096; (a) the
+// parent's walks / (b) this kernel, medians in ms).  (b) is 0.010-0.011 in
+// every cell, the rate at which calls are issued; the walks grow with M and
+// with the density:
+//   N = 16384, density 2/3: 0.025 / 0.045 / 0.060 / 0.112    1/4:  0.013 / 0.023 / 0.029 / 0.048
+//                     1/16: 0.0099 / 0.0127 / 0.0137 / 0.0177
+//   N = 4096,  density 2/3: 0.021 / 0.044 / 0.045 / 0.045    1/4:  0.011 / 0.023 / 0.023 / 0.023
+//                     1/16: 0.0101 / 0.0124 / 0.0125 / 0.0126
+// It wins past the parent's spread in every cell but (M = 1, 1/16), a tie at
+// either N.  So: every M <= 32 at a density of 1/4 and up, 8 <= M <= 32 at
+// 1/16 and up.  Not measured, so never: densities below 1/16, M = 2..7 at
+// 1/16, N < 4096 (fewer than 128 workgroups of 32 columns) and K < 4096.
+int call_i8_kernel(const PlanInput &in, int M, bool int8_acts)
+{
+    if (!int8_acts || M < 1 || in.i8_mode == 1 || !i8_eligible(in)) return 0;
+    const bool small = M <= kI8GemvMaxM && in.i8_small != 1;
+    if (in.i8_mode == 2) return small ? 2 : 1;
+    const int64_t kn = (int64_t)in.K * in.N;
+    if (in.nnz <= 0) return 0;
+    if ((M >= 64 && 4 * in.nnz >= kn) || (M >= 512 && 16 * in.nnz >= kn)) return 1;
+    if (small && in.K >= 4096 && in.N >= 4096 && (4 * in.nnz >= kn || (M >= 8 && 16 * in.nnz >= kn))) return 2;
+    return 0;
+}
+
 bool call_i8_mfma(const PlanInput &in, int M, bool int8_acts)
 {
-    if (!int8_acts || M < 1 || in.i8_mode == 1 || !i8_eligible(in)) return false;
-    if (in.i8_mode == 2) return true;
-    const int64_t kn = (int64_t)in.K * in.N;
-    return in.nnz > 0 && ((M >= 64 && 4 * in.nnz >= kn) || (M >= 512 && 16 * in.nnz >= kn));
+    return call_i8_kernel(in, M, int8_acts) != 0;
 }
 
 // Chunks of the host-pointer pipeline: one per ~16 MiB of Y (the PCIe leg

@@ -39,6 +39,7 @@ struct PlanInput {
     uint32_t bad_variants = 0;
     int jit_nch = 0;            // X^T chunks of the 128-row images (all widths)
     int i8_mode = 0;            // tcsc_hip_set_i8_mfma: 0 auto, 1 never, 2 every eligible call
+    int i8_small = 0;           // tcsc_hip_set_i8_small: 0 auto, 1 never the M <= 32 kernel (tsg_i8gemv.hip)
 };
 
 enum class Kernel { kRx, kJit128, kJit64, kEll, kEllPc };
@@ -69,7 +70,16 @@ CallPlan plan_call(const PlanInput &in, int M);
 // every eligible call there, 1 none; 0, the automatic rule, those the kernel
 // was measured to win by more than the add streams' own spread: M >= 64 at a
 // density nnz / (K N) of 1/4 and up, M >= 512 at 1/16 and up.
+//
+// Which integer kernel: call_i8_kernel is 0 for none, 1 for tsg_i8mfma_kernel
+// (128 x 128 tiles), 2 for tsg_i8gemv_kernel (tsg_i8gemv.hip: M <= 32, K split
+// across the waves of a workgroup -- allowed by the same exactness argument);
+// call_i8_mfma is "runs either".  Under i8_mode 2 every eligible call with
+// M <= 32 runs the second, unless i8_small is 1: then it runs what it ran
+// before that kernel existed (the tile kernel under mode 2).  Under mode 0 it
+// runs the second in the cells it was measured to win (tsg_plan.cpp).
 bool i8_eligible(const PlanInput &in);
+int call_i8_kernel(const PlanInput &in, int M, bool int8_acts);
 bool call_i8_mfma(const PlanInput &in, int M, bool int8_acts);
 
 // Logical workgroup ids of a weight-compiled call: M tiles x column tiles

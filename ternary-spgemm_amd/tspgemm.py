@@ -57,6 +57,7 @@ EXPORTED_SYMBOLS = (
     "tcsc_hip_gemm_dev_normquant", "tcsc_hip_gemm_prelu_dev_normquant",
     "tcsc_hip_gemm_dev_ex", "tsg_gemm_ex_check", "tsg_call_grid", "tcsc_hip_last_launch",
     "tcsc_hip_set_i8_mfma", "tcsc_hip_call_i8_mfma", "tsg_i8_build",
+    "tcsc_hip_call_i8_kernel", "tcsc_hip_set_i8_small", "tsg_i8gemv_pick",
 )
 
 # enum tsg_xtype (include/ternary_spgemm.h): element type of X on the _x calls
@@ -218,6 +219,9 @@ def lib() -> C.CDLL:
     L.tsg_jit_tile_map.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.tcsc_hip_set_i8_mfma.argtypes = [H, C.c_int]
     L.tcsc_hip_call_i8_mfma.argtypes = [H, C.c_int]
+    L.tcsc_hip_call_i8_kernel.argtypes = [H, C.c_int]
+    L.tcsc_hip_set_i8_small.argtypes = [H, C.c_int]
+    L.tsg_i8gemv_pick.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.tsg_i8_build.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int64, C.POINTER(C.c_int64),
                                C.POINTER(C.c_int32)]
     L.tcsc_hip_jit_width.argtypes = [H, C.c_int]
@@ -438,6 +442,14 @@ def ell_build(csp, csn, rip, rin, K: int, N: int, Cmax: int, MT: int, copies: in
            "tsg_ell_build")
     out = (ent.view(np.uint16), tab.reshape(-1, 2), c.value, nch.value)
     return out + (xb.value,) if with_xb else out
+
+
+def i8gemv_pick(K: int, N: int):
+    """(tile columns, waves) of tsg_i8gemv_kernel's launch on a K x N handle
+    (tsg_i8gemv_pick: host arithmetic, no device)."""
+    tn, S = C.c_int(), C.c_int()
+    _check(lib().tsg_i8gemv_pick(K, N, C.byref(tn), C.byref(S)), "tsg_i8gemv_pick")
+    return tn.value, S.value
 
 
 def i8_build(csp, csn, rip, rin, K: int, N: int, B: int = 0):
@@ -1220,6 +1232,17 @@ class TCSCDevice:
         """1 if an int8-activation call with M rows runs tsg_i8mfma_kernel
         under the handle's current mode, else 0."""
         return int(lib().tcsc_hip_call_i8_mfma(self._h, M))
+
+    def call_i8_kernel(self, M: int) -> int:
+        """Which integer kernel an int8-activation call with M rows runs under
+        the handle's current mode: 0 none, 1 tsg_i8mfma_kernel, 2
+        tsg_i8gemv_kernel (M <= 32)."""
+        return int(lib().tcsc_hip_call_i8_kernel(self._h, M))
+
+    def set_i8_small(self, mode: int) -> None:
+        """The M <= 32 integer kernel: 0 = by the set_i8_mfma rule (default),
+        1 = never (such calls run what they ran without it; tests and A/B)."""
+        _check(lib().tcsc_hip_set_i8_small(self._h, mode), "tcsc_hip_set_i8_small")
 
     def set_host_chunks(self, chunks: int) -> None:
         """Host-pointer calls: 0 = automatic M-chunk pipeline (default), n =
