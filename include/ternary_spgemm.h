@@ -515,6 +515,64 @@ int tcsc_hip_gemm_dev_ex(tsg_tcsc *h, const tsg_gemm_ex *d, int M, int N, int K,
 /* host only: no device, no handle */
 int tsg_gemm_ex_check(const tsg_gemm_ex *d, int M, int N, int K);
 
+/* The fused gate/up projection of a gated FFN (tsg_i8glu.hip):
+ * Y = act(gate(x)) * up(x) in ONE launch on the integer matrix cores, so that
+ * down(act(gate(x)) * up(x)) + h is two calls and U = up(x) is never stored.
+ * h_gate and h_up are two handles of one shape on one device; d is the
+ * descriptor above, unchanged: it describes the GATE projection and the output.
+ * db_up (float[N], required) and dcol_scale_up (float[N] or NULL) are the up
+ * projection's bias and column scale.
+ *
+ * Contract, in the words of tcsc_hip_gemm_dev_ex: fp32, one rounding per
+ * operation, no fused multiply-add, no contraction.
+ *
+ *   q, rs = the int8 activations and the per-row scale of d's in_mode
+ *           (TSG_IN_PLAIN: dX is int8, rs = d->drow_scale or none; ACTQUANT /
+ *           NORMQUANT: made ONCE by the row pass, rs = deq, also written to
+ *           drow_scale_out)
+ *   u = ((chain_up[m,n]   * rs[m]) * dcol_scale_up[n]) + db_up[n]
+ *   y = ((chain_gate[m,n] * rs[m]) * d->dcol_scale[n]) + d->db[n]
+ *                                       (a NULL scale: that multiply is not performed)
+ *   a = act(y)                          NONE, PRELU, RELU, RELU2 as above
+ *   a = a * u                           rounded; never contracted with what follows
+ *   if (dmul) a = a * widen(mul)        then exactly the tail of _dev_ex: dadd, the
+ *   if (dadd) a = a + widen(add)        in-place rule, one rounding to ytype, ldY,
+ *                                       the written-range guarantee
+ *
+ * So with d->dmul NULL the result is byte for byte tcsc_hip_gemm_dev_ex(h_gate,
+ * d') with d' = d and dmul = U (fp32, ldmul = N), U the fp32 Y of
+ * tcsc_hip_gemm_dev_ex(h_up, ...) with the same input fields, TSG_ACT_NONE,
+ * dcol_scale_up and db_up; drow_scale_out holds what either of those writes.
+ * Both chains are exact integers (tcsc_hip_set_i8_mfma below), so a * u is one
+ * more fp32 multiply of the epilogue that exists.
+ * Kernels.  Always the integer kernels, whatever tcsc_hip_set_i8_mfma says
+ * (it chooses between kernels that store the same bytes; this call has one
+ * family): 1 <= M <= 32 the split-K variant tsg_i8glu_gemv_kernel, larger M
+ * tsg_i8glu_kernel (128 rows x 64 columns of both matrices per workgroup).
+ * Errors.  TSG_ERR_ARG naming the field or the handle, nothing enqueued:
+ * whatever tsg_gemm_ex_check refuses; a NULL db_up; TSG_IN_PLAIN with an xtype
+ * other than TSG_X_I8 (an unquantised fp32 / fp16 / bf16 X has no matrix path);
+ * a handle without an image (BlockedTCSC, K > 131072); two handles that differ
+ * in K, N or device, or do not match the call's N and K; an M too large for one
+ * launch (as on the int8 calls); during stream capture an image or a scratch
+ * that is not ready, naming tcsc_hip_reserve_glu.  tsg_gemm_glu_check performs
+ * the checks that need no handle on the host.
+ * Handles.  The quantising scratch, the kernel timing and the ordering between
+ * streams are h_gate's; h_up contributes its image only.  The two handles'
+ * locks are never held together: glu(a, b) and glu(b, a) from two threads do
+ * not deadlock.  tcsc_hip_reserve_glu builds both images and sizes h_gate's
+ * int8 scratch for max_M rows (tcsc_hip_reserve builds an image only where the
+ * automatic rule routes a call: not enough for capturing this one).
+ * Out of scope: a fallback for handles without an image or an unquantised X;
+ * SiLU / SwiGLU (no bit-exact exp contract); quantising Y for the down
+ * projection; the host-pointer calls, the plugin header and ShardedTCSC.
+ * Extension: no reference counterpart. */
+int tcsc_hip_gemm_dev_glu(tsg_tcsc *h_gate, tsg_tcsc *h_up, const tsg_gemm_ex *d, const float *db_up,
+                          const float *dcol_scale_up, int M, int N, int K, void *stream);
+/* host only: no device, no handle */
+int tsg_gemm_glu_check(const tsg_gemm_ex *d, const float *db_up, int M, int N, int K);
+int tcsc_hip_reserve_glu(tsg_tcsc *h_gate, tsg_tcsc *h_up, int max_M);
+
 /* Pre-allocates the per-handle work buffer for row counts up to max_M and, on
  * the weight-compiled kernel, compiles every code image a call with M <= max_M
  * rows runs (and the small-M images), so no later such call allocates or

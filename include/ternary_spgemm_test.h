@@ -164,6 +164,12 @@ int tsg_i8_build(const int32_t *col_start_pos, const int32_t *col_start_neg, con
 int tcsc_hip_set_i8_small(tsg_tcsc *h, int mode);
 int tsg_i8gemv_pick(int K, int N, int *tile_cols, int *waves);
 
+/* The split-K variant of the fused gate/up call (tsg_i8glu_gemv_kernel, M <=
+ * 32; tcsc_hip_gemm_dev_glu): the columns of a workgroup's tile (32) and its
+ * waves (1, 2, 4 or 8: the largest within the k-steps).  Host only.
+ * tcsc_hip_set_i8_small(h_gate, 1) sends such a call to the tile variant. */
+int tsg_i8glu_pick(int K, int N, int *tile_cols, int *waves);
+
 /* The rx kernel's block stream (tsg_tcsc_rx_kernel, the path of a W too large
  * for one compiled image; csrc/tsg_internal.h RxImage): per (256-column tile,
  * wave) the first dword of that wave's stream in wstart, the stream's blocks

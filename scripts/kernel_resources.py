@@ -43,6 +43,7 @@ def units():
     nopk = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
     out.append(("tsg_i8mfma", "tsg_i8mfma.hip", nopk))
     out.append(("tsg_i8gemv", "tsg_i8gemv.hip", nopk))
+    out.append(("tsg_i8glu", "tsg_i8glu.hip", nopk))
     return out
 
 

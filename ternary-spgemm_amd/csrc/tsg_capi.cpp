@@ -594,6 +594,39 @@ int run_i8(tsg_tcsc *h, Call &c, int kernel)
     return rc || !c.quant ? rc : work_end(h, c);
 }
 
+// The fused gate/up call (tcsc_hip_gemm_dev_glu; tsg_i8glu.hip) on the gate
+// handle h, c.out carrying the up side (the up handle's image was looked up
+// under its own lock, which is no longer held: never two handles' locks at
+// once).  run_i8 with two images: the scratch, the timing and the work event
+// are the gate handle's.  Always the integer kernels, whatever i8_mode says;
+// i8_small sends M <= 32 to the tile variant too.
+int run_glu(tsg_tcsc *h, Call &c)
+{
+    const int M = c.in.M;
+    const size_t q8 = std::max<size_t>((size_t)M * h->plan.K, 16);
+    if (c.capturing && ((c.quant && (((size_t)M + 127) / 128 * 128 > h->aq_rows || q8 > h->aq8_bytes)) || !h->d_i8))
+        return fail(TSG_ERR_ARG, "M=" + std::to_string(M) + " needs the gate handle's int8 matrix-core image and "
+                                 "quantisation scratch, which are not ready during stream capture; call "
+                                 "tcsc_hip_reserve_glu(h_gate, h_up, max_M) before capturing");
+    if (((int64_t)M + tsg::kI8TileM - 1) / tsg::kI8TileM * (((int64_t)h->plan.N + tsg::kI8TileN - 1) / tsg::kI8TileN) >=
+        (1ll << 31) / 256)
+        return fail(TSG_ERR_ARG, "M=" + std::to_string(M) + " is too large for one launch; split the rows");
+    int rc = ensure_i8(h);
+    if (rc) return rc;
+    if (c.quant) {
+        rc = stage_begin(h, CallPlan{}, c, true);
+        if (rc) return rc;
+        c.in.X = h->d_aq8, c.in.xtype = tsg::kXI8;
+    }
+    int slot;
+    rc = timing_begin(h, c.capturing, c.s(), slot);
+    if (rc) return rc;
+    if (tsg::launch_tcsc_i8glu(static_cast<const int8_t *>(c.in.X), h->d_i8, h->plan.K, c.out, h->plan.i8_small == 1) != 0)
+        return fail(TSG_ERR_HIP, std::string("fused gate/up kernel launch: ") + hipGetErrorString(hipGetLastError()));
+    rc = timing_end(h, slot, c.s());
+    return rc || !c.quant ? rc : work_end(h, c);
+}
+
 // the register-X walk: X^T pass, then the kernel
 int run_rx(tsg_tcsc *h, const CallPlan &p, Call &c)
 {
@@ -1758,11 +1791,9 @@ extern "C" int tsg_gemm_ex_check(const tsg_gemm_ex *d, int M, int N, int K)
     return TSG_OK;
 }
 
-extern "C" int tcsc_hip_gemm_dev_ex(tsg_tcsc *h, const tsg_gemm_ex *d, int M, int N, int K, void *stream)
+// a checked descriptor as the Call it restates
+static Call ex_call(const tsg_gemm_ex *d, int M, int N, int K, void *stream)
 {
-    if (!h) return fail(TSG_ERR_ARG, "null handle");
-    const int rc = tsg_gemm_ex_check(d, M, N, K);
-    if (rc) return rc;
     // the epilogue as the kernels take it; an operand that is exactly Y (the
     // in-place form) is marked, so that the kernel loads it through Y itself
     tsg::Epi ep;
@@ -1784,7 +1815,97 @@ extern "C" int tcsc_hip_gemm_dev_ex(tsg_tcsc *h, const tsg_gemm_ex *d, int M, in
     c.out.rs = d->drow_scale, c.out.cs = d->dcol_scale, c.out.ep = ep;
     c.quant = d->in_mode != TSG_IN_PLAIN, c.drs_out = d->drow_scale_out;
     c.norm = d->in_mode == TSG_IN_NORMQUANT, c.in.g = d->dgamma, c.eps = d->eps;
-    return run_dev(h, c);
+    return c;
+}
+
+extern "C" int tcsc_hip_gemm_dev_ex(tsg_tcsc *h, const tsg_gemm_ex *d, int M, int N, int K, void *stream)
+{
+    if (!h) return fail(TSG_ERR_ARG, "null handle");
+    const int rc = tsg_gemm_ex_check(d, M, N, K);
+    if (rc) return rc;
+    return run_dev(h, ex_call(d, M, N, K, stream));
+}
+
+// The fused gate/up call (include/ternary_spgemm.h; tsg_i8glu.hip): the
+// descriptor call on h_gate whose epilogue multiplies by the up projection,
+// computed by the same kernel from h_up's image
+extern "C" int tsg_gemm_glu_check(const tsg_gemm_ex *d, const float *db_up, int M, int N, int K)
+{
+    const int rc = tsg_gemm_ex_check(d, M, N, K);
+    if (rc) return rc;
+    if (!db_up) return fail(TSG_ERR_ARG, "db_up is NULL: the up projection has a bias of its own");
+    if (d->in_mode == TSG_IN_PLAIN && d->xtype != TSG_X_I8)
+        return fail(TSG_ERR_ARG, "xtype=" + std::to_string(d->xtype) + " in TSG_IN_PLAIN: the fused gate/up call takes "
+                                 "int8 activations only (TSG_X_I8, or a quantising in_mode)");
+    return TSG_OK;
+}
+
+// what tcsc_hip_gemm_dev_glu and tcsc_hip_reserve_glu ask of their two handles
+static int glu_handles(const tsg_tcsc *hg, const tsg_tcsc *hu)
+{
+    if (!hg) return fail(TSG_ERR_ARG, "h_gate: null handle");
+    if (!hu) return fail(TSG_ERR_ARG, "h_up: null handle");
+    for (const tsg_tcsc *h : {hg, hu})
+        if (!tsg::i8_eligible(h->plan))
+            return fail(TSG_ERR_ARG, std::string(h == hg ? "h_gate" : "h_up") + " has no int8 matrix-core image "
+                                     "(a BlockedTCSC handle, or K > 131072)");
+    if (hg->plan.K != hu->plan.K || hg->plan.N != hu->plan.N || hg->device != hu->device)
+        return fail(TSG_ERR_ARG, "h_gate (K=" + std::to_string(hg->plan.K) + " N=" + std::to_string(hg->plan.N) +
+                                 " device " + std::to_string(hg->device) + ") and h_up (K=" + std::to_string(hu->plan.K) +
+                                 " N=" + std::to_string(hu->plan.N) + " device " + std::to_string(hu->device) +
+                                 ") differ");
+    return TSG_OK;
+}
+
+extern "C" int tcsc_hip_gemm_dev_glu(tsg_tcsc *h_gate, tsg_tcsc *h_up, const tsg_gemm_ex *d, const float *db_up,
+                                     const float *dcol_scale_up, int M, int N, int K, void *stream)
+{
+    int rc = glu_handles(h_gate, h_up);
+    if (!rc) rc = tsg_gemm_glu_check(d, db_up, M, N, K);
+    if (rc) return rc;
+    Call c = ex_call(d, M, N, K, stream);
+    c.out.b_up = db_up, c.out.cs_up = dcol_scale_up;
+    rc = check_call(h_gate, c);
+    if (rc || M == 0 || N == 0) return rc;
+    DeviceGuard g(h_gate->device);
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    HIP_TRY(hipStreamIsCapturing(c.s(), &cap));
+    c.capturing = cap != hipStreamCaptureStatusNone;
+    {  // the up handle contributes its image, under its own lock
+        std::lock_guard<std::mutex> lk(h_up->mu);
+        if (!h_up->d_i8 && c.capturing)
+            return fail(TSG_ERR_ARG, "h_up's int8 matrix-core image is not built yet; call "
+                                     "tcsc_hip_reserve_glu(h_gate, h_up, max_M) before capturing");
+        rc = ensure_i8(h_up);
+        if (rc) return rc;
+        c.out.img_up = h_up->d_i8;
+    }
+    std::lock_guard<std::mutex> lk(h_gate->mu);
+    return run_glu(h_gate, c);
+}
+
+extern "C" int tcsc_hip_reserve_glu(tsg_tcsc *h_gate, tsg_tcsc *h_up, int max_M)
+{
+    int rc = glu_handles(h_gate, h_up);
+    if (rc) return rc;
+    if (max_M < 0) return fail(TSG_ERR_ARG, "max_M < 0");
+    DeviceGuard g(h_gate->device);
+    {
+        std::lock_guard<std::mutex> lk(h_up->mu);
+        rc = ensure_i8(h_up);
+        if (rc) return rc;
+    }
+    std::lock_guard<std::mutex> lk(h_gate->mu);
+    rc = ensure_i8(h_gate);
+    return rc ? rc : ensure_aq(h_gate, max_M, std::max<size_t>((size_t)std::max(max_M, 1) * h_gate->plan.K, 16), false);
+}
+
+extern "C" int tsg_i8glu_pick(int K, int N, int *tile_cols, int *waves)
+{
+    if (K < 0 || N < 0) return fail(TSG_ERR_ARG, "tsg_i8glu_pick: K < 0 or N < 0");
+    if (tile_cols) *tile_cols = 32;
+    if (waves) *waves = tsg::i8glu_pick(K);
+    return TSG_OK;
 }
 
 extern "C" int tcsc_hip_info(const tsg_tcsc *h, tsg_info *o)

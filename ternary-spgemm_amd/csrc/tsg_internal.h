@@ -81,6 +81,10 @@ struct YOut {
     int M = 0, N = 0;
     bool prelu = false;
     void *stream = nullptr;
+    // the up side of a fused gate/up call (tsg_i8glu.hip; null on every other
+    // call): the up handle's packed image, its bias and its column scale
+    const uint32_t *img_up = nullptr;
+    const float *b_up = nullptr, *cs_up = nullptr;
     bool scaled() const { return rs != nullptr || cs != nullptr; }
     // the ytype argument as a kernel receives it; wants_scaled: this kernel tests kYScaled
     int kernel_ytype(bool wants_scaled) const { return ytype | (wants_scaled && scaled() ? kYScaled : 0) | (ep.on() ? kYEpi : 0); }
@@ -465,6 +469,23 @@ inline I8GemvPick i8gemv_pick(int K, int N)
 }
 // X: int8 [M][K] row-major, M <= kI8GemvMaxM; img: the i8mfma image, uploaded
 int launch_tcsc_i8gemv(const int8_t *X, const uint32_t *img, int K, const YOut &o);
+
+// "i8glu" kernels (tsg_i8glu.hip): act(gate(x)) * up(x) in one launch over the
+// images of two handles of one shape (o.img_up, o.b_up, o.cs_up: the up side).
+// tsg_i8glu_kernel: 128 rows x 64 columns of both matrices per workgroup;
+// tsg_i8glu_gemv_kernel (1 <= M <= kI8GemvMaxM unless `tile`): one workgroup per
+// 32 columns, its S waves splitting the k-steps, S x 32 x 256 bytes of LDS.
+// i8glu_pick: S, the largest of 1, 2, 4, 8 that is at most the k-steps (8: the
+// 64 KiB of kI8GemvLds).
+constexpr int kI8GluWaves = kI8GemvLds / (32 * 256);
+inline int i8glu_pick(int K)
+{
+    const int nks = (K + kI8KStep - 1) / kI8KStep;
+    int S = 1;
+    while (2 * S <= kI8GluWaves && 2 * S <= nks) S *= 2;
+    return S;
+}
+int launch_tcsc_i8glu(const int8_t *X, const uint32_t *img, int K, const YOut &o, bool tile);
 
 // Environment knobs (csrc/tsg_knobs.cpp): A/B studies and tests, none of
 // which changes a result.  knob_check: "" when every set knob has an

@@ -58,6 +58,7 @@ EXPORTED_SYMBOLS = (
     "tcsc_hip_gemm_dev_ex", "tsg_gemm_ex_check", "tsg_call_grid", "tcsc_hip_last_launch",
     "tcsc_hip_set_i8_mfma", "tcsc_hip_call_i8_mfma", "tsg_i8_build",
     "tcsc_hip_call_i8_kernel", "tcsc_hip_set_i8_small", "tsg_i8gemv_pick",
+    "tcsc_hip_gemm_dev_glu", "tsg_gemm_glu_check", "tcsc_hip_reserve_glu", "tsg_i8glu_pick",
 )
 
 # enum tsg_xtype (include/ternary_spgemm.h): element type of X on the _x calls
@@ -222,6 +223,10 @@ def lib() -> C.CDLL:
     L.tcsc_hip_call_i8_kernel.argtypes = [H, C.c_int]
     L.tcsc_hip_set_i8_small.argtypes = [H, C.c_int]
     L.tsg_i8gemv_pick.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.tsg_i8glu_pick.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.tcsc_hip_gemm_dev_glu.argtypes = [H, H, C.POINTER(tsg_gemm_ex), vp, vp, C.c_int, C.c_int, C.c_int, vp]
+    L.tsg_gemm_glu_check.argtypes = [C.POINTER(tsg_gemm_ex), vp, C.c_int, C.c_int, C.c_int]
+    L.tcsc_hip_reserve_glu.argtypes = [H, H, C.c_int]
     L.tsg_i8_build.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int64, C.POINTER(C.c_int64),
                                C.POINTER(C.c_int32)]
     L.tcsc_hip_jit_width.argtypes = [H, C.c_int]
@@ -452,6 +457,14 @@ def i8gemv_pick(K: int, N: int):
     return tn.value, S.value
 
 
+def i8glu_pick(K: int, N: int):
+    """(tile columns, waves) of tsg_i8glu_gemv_kernel's launch, the M <= 32
+    variant of the fused gate/up call (tsg_i8glu_pick: host arithmetic)."""
+    tn, S = C.c_int(), C.c_int()
+    _check(lib().tsg_i8glu_pick(K, N, C.byref(tn), C.byref(S)), "tsg_i8glu_pick")
+    return tn.value, S.value
+
+
 def i8_build(csp, csn, rip, rin, K: int, N: int, B: int = 0):
     """Host view of the integer matrix-core kernel's image (tsg_i8_build,
     include/ternary_spgemm_test.h): (img uint32[], geom = (Kp, Np, tile rows,
@@ -634,6 +647,12 @@ def gemm_ex_check(desc, M: int, N: int, K: int) -> None:
     device, no handle.  desc: a tsg_gemm_ex or None (a NULL descriptor).  Raises
     TSGError naming the field that is wrong."""
     _check(lib().tsg_gemm_ex_check(None if desc is None else C.byref(desc), M, N, K), "tsg_gemm_ex_check")
+
+
+def gemm_glu_check(desc, db_up, M: int, N: int, K: int) -> None:
+    """The host-side checks of the fused gate/up call (tsg_gemm_glu_check):
+    gemm_ex_check's, a db_up that is not NULL, and int8 activations."""
+    _check(lib().tsg_gemm_glu_check(None if desc is None else C.byref(desc), db_up, M, N, K), "tsg_gemm_glu_check")
 
 
 _host_register_ok = None
@@ -1003,8 +1022,55 @@ class TCSCDevice:
         type.  add=Y (or mul=Y) is the in-place form, h += proj(x).  The result
         is epilogue_ref(...) of the fp32 call's value, rounded once to Y's
         dtype, bit for bit.  Returns Y."""
+        d, M, Y, stream = self._ex_desc("gemm_torch_ex", X, b, Y, act, alpha, mul, add, out_dtype, row_scale, col_scale,
+                                        quant, gamma, eps, row_scale_out)
+        self.gemm_dev_ex(d, M, stream)
+        return Y
+
+    def gemm_dev_glu(self, up, desc, db_up: int, dcol_scale_up: Optional[int], M: int, stream: int = 0) -> None:
+        """The fused gate/up call (tcsc_hip_gemm_dev_glu) on this handle as the
+        gate: desc describes the gate projection and the output, up is the
+        TCSCDevice of the up projection (same K, N and device), db_up its bias
+        and dcol_scale_up its column scale (device pointers; the scale may be
+        None)."""
+        _check(lib().tcsc_hip_gemm_dev_glu(self._h, up._h, None if desc is None else C.byref(desc), db_up,
+                                           dcol_scale_up, M, self.N, self.K, stream or None), "tcsc_hip_gemm_dev_glu")
+
+    def gemm_torch_glu(self, up, X, b, b_up, Y=None, act="relu2", alpha=None, mul=None, add=None, out_dtype=None,
+                       row_scale=None, col_scale=None, col_scale_up=None, quant=None, gamma=None, eps=None,
+                       row_scale_out=None):
+        """The gate and up projections of a gated FFN in one launch on the
+        integer matrix cores: Y = cast(act(gate(X)) * up(X) * mul + add), this
+        handle the gate, `up` the TCSCDevice of the up projection.  X is int8
+        (row_scale allowed) or, with quant "act" / "norm", float32 / float16 /
+        bfloat16, quantised once for both projections.  b_up and col_scale_up
+        are the up projection's bias and column scale; everything else as on
+        gemm_torch_ex.  The result is, bit for bit, gemm_torch_ex(..., mul=U) on
+        this handle with U = up.gemm_torch_ex(X, b_up, act="none",
+        col_scale=col_scale_up, ...) in float32 (and `mul`, when given,
+        multiplied in after U).  Returns Y."""
+        where = "gemm_torch_glu"
+        if not isinstance(up, TCSCDevice):
+            raise TSGError(1, where, f"up must be a TCSCDevice, got {type(up)}")
+        d, M, Y, stream = self._ex_desc(where, X, b, Y, act, alpha, mul, add, out_dtype, row_scale, col_scale, quant,
+                                        gamma, eps, row_scale_out, b_up=b_up, col_scale_up=col_scale_up)
+        if b_up is None:
+            raise TSGError(1, where, "b_up is required")
+        self.gemm_dev_glu(up, d, b_up.data_ptr(), None if col_scale_up is None else col_scale_up.data_ptr(), M, stream)
+        return Y
+
+    def reserve_glu(self, up, max_M: int) -> None:
+        """Builds both handles' int8 matrix-core images and sizes this (the
+        gate) handle's quantisation scratch for max_M rows, so that
+        gemm_torch_glu calls with M <= max_M can be captured in a graph."""
+        _check(lib().tcsc_hip_reserve_glu(self._h, up._h, max_M), "tcsc_hip_reserve_glu")
+
+    def _ex_desc(self, where, X, b, Y, act, alpha, mul, add, out_dtype, row_scale, col_scale, quant, gamma, eps,
+                 row_scale_out, **more):
+        """The argument checks of gemm_torch_ex and the descriptor it fills.
+        more: further float32 [N] tensors checked like b (name=tensor).
+        Returns (descriptor, M, Y, the current stream)."""
         import torch
-        where = "gemm_torch_ex"
         dev = torch.device("cuda", self.device)
         ytypes = {torch.float32: TSG_Y_F32, torch.float16: TSG_Y_F16, torch.bfloat16: TSG_Y_BF16}
         xtypes = {torch.float32: TSG_X_F32, torch.float16: TSG_X_F16, torch.bfloat16: TSG_X_BF16,
@@ -1023,7 +1089,7 @@ class TCSCDevice:
         M = X.shape[0]
         for name, t, shape in (("b", b, (self.N,)), ("alpha", alpha, (self.N,)), ("row_scale", row_scale, (M,)),
                                ("col_scale", col_scale, (self.N,)), ("row_scale_out", row_scale_out, (M,)),
-                               ("gamma", gamma, (self.K,))):
+                               ("gamma", gamma, (self.K,)), *((n, t, (self.N,)) for n, t in more.items())):
             if t is None:
                 continue
             if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != dev or \
@@ -1069,8 +1135,7 @@ class TCSCDevice:
         if add is not None:
             d.ldadd = rows("add", add)
             d.dadd, d.addtype = add.data_ptr(), ytypes[add.dtype]
-        self.gemm_dev_ex(d, M, torch.cuda.current_stream(dev).cuda_stream)
-        return Y
+        return d, M, Y, torch.cuda.current_stream(dev).cuda_stream
 
     def _torch_xy(self, where, X, b, Y, alpha, out_dtype, narrow_y, scaled=False, row_scale=None, col_scale=None,
                   row_scale_out=None, actquant=False, norm=False, gamma=None, eps=None):
