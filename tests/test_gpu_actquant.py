@@ -43,7 +43,7 @@ import functools
 import numpy as np
 import pytest
 
-from test_gpu_ldy import SENT, _bits, _dev, _jit_handle
+from test_gpu_ldy import SENT, _bits, _dev, _jit_handle, _pin_streams
 from test_gpu_scaled import _draw_scales, _got_bits, _outputs, _ybits_of, expect32
 from test_gpu_xtype import _tdtype, _x_on_device
 from test_gpu_ytype import SENT16, YMAX, _fill16
@@ -320,6 +320,7 @@ def test_actquant_rx_kernel(tsg, monkeypatch):
     case = _acase(M, K, N)
     h = tsg.TCSCDevice(*case[0], K, N)
     h.set_small_m(1)
+    _pin_streams(h, M)
     assert h.kernel_name() == "tsg_tcsc_rx_kernel" and h.call_kernel(M) == "tsg_tcsc_rx_kernel"
     check_actquant(h, case, "float32", ("rx", M, K, N))
     h.close()
@@ -341,6 +342,7 @@ def test_actquant_blocked_handle(tsg):
 def _type_handle(tsg, arrays, family, M, K, N):
     if family == "walk":
         h = tsg.TCSCDevice(*arrays, K, N)
+        _pin_streams(h, M)
         assert h.call_kernel(M) == "tsg_tcsc_ell_kernel"
     else:
         h = _jit_handle(tsg, arrays, K, N, 64, 16)
@@ -535,6 +537,7 @@ def test_actquant_graph_capture_after_reserve(tsg):
     want2, deq2 = expected_bits(run, Xw2, b, alpha, cs, "bfloat16")
     assert not np.array_equal(want2[(True, "plain")], want[(True, "plain")])
     h = tsg.TCSCDevice(*arrays, K, N)
+    _pin_streams(h, M)
     assert h.call_kernel(M) == "tsg_jit64_kernel"
     h.reserve(M)
     work = h.info()["work_bytes"]
@@ -572,6 +575,7 @@ def test_actquant_capture_without_reserve_fails_loudly(tsg, family):
     arrays, Xt, Xw, b, alpha, cs, deq, want = _acase(M, K, N, "bfloat16", "float32")
     if family == "walk":
         h = tsg.TCSCDevice(*arrays, K, N)
+        _pin_streams(h, M)
         assert h.call_kernel(M) == "tsg_tcsc_ell_kernel"
     else:
         h = _jit_handle(tsg, arrays, K, N, 64, 8)

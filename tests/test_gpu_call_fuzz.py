@@ -462,6 +462,7 @@ def _handle(tsg, c, arrays):
         rows = 64 if c.family == "rows64" else 128
         h = _jit_handle(tsg, arrays, K, N, rows, c.width)
         assert h.call_kernel(M) == KERNEL[c.family] and h.call_tile_rows(M) == rows, (c, h.call_kernel(M))
+        assert h.call_i8_kernel(M) == 0, (c, h.call_i8_kernel(M))  # (_jit_handle pins the add streams)
         if c.width:
             assert h.jit_width(M) == c.width and h.jit_waves(M) == 8, (c, h.jit_width(M), h.jit_waves(M))
         return h
@@ -469,10 +470,14 @@ def _handle(tsg, c, arrays):
         h = tsg.TCSCDevice.from_blocked(*arrays, K, N, c.B)
     else:
         h = tsg.TCSCDevice(*arrays, K, N)
+        # the add streams for the int8-activation calls too: call_kernel names the stream plan, and in
+        # its automatic mode a plain handle leaves it for tsg_i8mfma_kernel by M and W's density
+        h.set_i8_mfma(1)
     h.set_small_m(c.mode)
     if c.family == "rx":
         assert h.kernel_name() == KERNEL["rx"], (c, h.kernel_name())
     assert h.call_kernel(M) == KERNEL[c.family], (c, h.call_kernel(M))
+    assert h.call_i8_kernel(M) == 0, (c, h.call_i8_kernel(M))  # (a blocked handle is never eligible)
     if c.family in ("pc", "walk"):
         assert h.call_tile_rows(M) == 0, c
     return h

@@ -45,7 +45,7 @@ import types
 import numpy as np
 import pytest
 
-from test_gpu_ldy import SENT, _assert_only_view_written, _dev, _fill, _jit_handle
+from test_gpu_ldy import SENT, _assert_only_view_written, _dev, _fill, _jit_handle, _pin_streams
 from test_gpu_scaled import _chains, _got_bits, _outputs, _ybits_of, expect32
 from test_gpu_xtype import _tdtype
 from test_gpu_ytype import SENT16, YMAX, _assert_only_view_written16, _cast_bits, _fill16, _ybits, torch_from_bits
@@ -266,7 +266,10 @@ def open_handle(tsg, monkeypatch, name, arrays, shape=None):
         h.set_small_m(1)
     else:
         h = _jit_handle(tsg, arrays, K, N, 64 if fam == "rows64" else 128, width)
+    if fam != "blocked":  # (a blocked handle is never eligible for the integer kernels)
+        _pin_streams(h, M)
     assert h.call_kernel(M) == KERNEL[fam], (name, h.call_kernel(M))
+    assert h.call_i8_kernel(M) == 0, (name, h.call_i8_kernel(M))
     if fam in ("rows64", "rows128"):
         assert h.call_tile_rows(M) == (64 if fam == "rows64" else 128)
         if width:
@@ -524,6 +527,7 @@ def test_epilogue_operand_alignment(tsg, monkeypatch, name, opdtype):
     else:
         h = _jit_handle(tsg, ec.arrays, K, N, 64, width)
         assert h.jit_width(M) == width
+    _pin_streams(h, M)
     assert h.call_kernel(M) == KERNEL[fam]
     inp = Inputs(ec)
     ex = expect(key, "relu2", opdtype, opdtype, opdtype)

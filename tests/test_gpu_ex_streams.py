@@ -17,7 +17,7 @@ they do."""
 import numpy as np
 import pytest
 
-from test_gpu_ldy import _dev
+from test_gpu_ldy import _dev, _pin_streams
 from test_gpu_scaled import _got_bits, _ybits_of, expect32
 from test_gpu_xtype import _tdtype
 
@@ -112,6 +112,7 @@ def test_ex_two_streams_on_the_images(tsg, oracle_mod):
     K, N, M = 2048, 4096, 1024
     t = O.tcsc_encode(O.gen_ternary(K, N, 4, 21))
     h = tsg.TCSCDevice(*t.arrays, K, N)
+    _pin_streams(h, M)  # (the automatic rule sends this shape to tsg_i8mfma_kernel: no work buffer, no rn)
     h.reserve(M)
     assert h.call_kernel(M) != "tsg_tcsc_ell_kernel"
     _two_streams(tsg, O, h, t, M, K, N, np.r_[0:64, M - 64:M], 4, ("norm", "act"))
@@ -125,6 +126,7 @@ def test_ex_two_streams_on_the_walks_int8_copy(tsg, oracle_mod):
     K, N, M = 2048, 4096, 16
     t = O.tcsc_encode(O.gen_ternary(K, N, 4, 21))
     h = tsg.TCSCDevice(*t.arrays, K, N)
+    _pin_streams(h, M)
     h.set_small_m(2)
     h.reserve(M)
     assert h.call_kernel(M) == "tsg_tcsc_ell_kernel"
@@ -142,6 +144,7 @@ def test_ex_scratch_hand_over(tsg, oracle_mod):
     M, K, N = 64, 388, 700
     t = O.tcsc_encode(O.gen_ternary(K, N, 4, 1000 * M + K + N))
     h = tsg.TCSCDevice(*t.arrays, K, N)
+    _pin_streams(h, M)
     assert h.call_kernel(M) == "tsg_jit64_kernel"
     rows = np.arange(M)
     b = np.linspace(-3, 3, N).astype(F)

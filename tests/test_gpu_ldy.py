@@ -121,8 +121,20 @@ def test_ldy_small_m_walks(tsg, M, K, N, mode, kernel):
     h.close()
 
 
+def _pin_streams(h, M=None):
+    """The add streams for the int8-activation calls too: in its automatic mode
+    a plain handle sends such calls to tsg_i8mfma_kernel by M and W's density
+    (tsg_plan.cpp call_i8_kernel), whatever call_kernel names.  Without M: the
+    rule's thresholds and one M past them."""
+    h.set_i8_mfma(1)
+    for m in (M,) if M is not None else (32, 64, 512, 4096):
+        assert h.call_i8_kernel(m) == 0 and h.call_i8_mfma(m) == 0, m
+    return h
+
+
 def _jit_handle(tsg, arrays, K, N, rows, width):
     h = tsg.TCSCDevice(*arrays, K, N)
+    _pin_streams(h)
     h.set_small_m(1)
     h.set_tile_rows(rows)
     if width:

@@ -57,7 +57,7 @@ import pytest
 
 import test_gpu_actquant as A
 from test_gpu_actquant import FAMILY_SHAPES, TYPE_SHAPES, XDTYPES, YDTYPES
-from test_gpu_ldy import SENT, _bits, _dev, _jit_handle
+from test_gpu_ldy import SENT, _bits, _dev, _jit_handle, _pin_streams
 from test_gpu_scaled import _draw_scales, _got_bits, _outputs
 from test_gpu_xtype import _tdtype, _x_on_device
 from test_gpu_ytype import SENT16, _fill16
@@ -408,6 +408,7 @@ def test_normquant_rx_kernel(tsg, monkeypatch):
     case = _ncase(M, K, N)
     h = tsg.TCSCDevice(*case[0], K, N)
     h.set_small_m(1)
+    _pin_streams(h, M)
     assert h.kernel_name() == "tsg_tcsc_rx_kernel" and h.call_kernel(M) == "tsg_tcsc_rx_kernel"
     check_normquant(h, case, "float32", ("rx", M, K, N))
     h.close()
@@ -690,6 +691,7 @@ def test_normquant_graph_capture_after_reserve(tsg):
     want2, deq2 = A.expected_bits(run, tsg.rms_norm_ref(Xw2, g, eps)[0], b, alpha, cs, "bfloat16")
     assert not np.array_equal(want2[(True, "plain")], want[(True, "plain")])
     h = tsg.TCSCDevice(*arrays, K, N)
+    _pin_streams(h, M)
     assert h.call_kernel(M) == "tsg_jit64_kernel"
     h.reserve(M)
     work = h.info()["work_bytes"]
@@ -726,6 +728,7 @@ def test_normquant_capture_without_reserve_fails_loudly(tsg, family):
     arrays, Xt, Xw, g, eps, b, alpha, cs, deq, want, xn = _ncase(M, K, N, "bfloat16", "float32")
     if family == "walk":
         h = tsg.TCSCDevice(*arrays, K, N)
+        _pin_streams(h, M)
         assert h.call_kernel(M) == "tsg_tcsc_ell_kernel"
     else:
         h = _jit_handle(tsg, arrays, K, N, 64, 8)

@@ -38,7 +38,7 @@ import os
 import numpy as np
 import pytest
 
-from test_gpu_ldy import SENT, _assert_only_view_written, _bits, _dev, _fill, _jit_handle
+from test_gpu_ldy import SENT, _assert_only_view_written, _bits, _dev, _fill, _jit_handle, _pin_streams
 from test_gpu_xtype import _tdtype
 from test_gpu_ytype import (SENT16, YMAX, _assert_only_view_written16, _cast_bits, _fill16, _x_for, _ybits,
                             torch_from_bits)
@@ -258,6 +258,7 @@ def test_scaled_rx_kernel(tsg, monkeypatch, ydtype):
     case = _scase(M, K, N, "float32", ydtype)
     h = tsg.TCSCDevice(*case[0], K, N)
     h.set_small_m(1)
+    _pin_streams(h, M)
     assert h.kernel_name() == "tsg_tcsc_rx_kernel" and h.call_kernel(M) == "tsg_tcsc_rx_kernel"
     check_scaled(h, case, ydtype, ("rx", M, K, N))
     h.close()
@@ -396,6 +397,7 @@ def test_scaled_special_scale_values(tsg, family):
     cs[N - 1] = np.float32(np.nan)  # the last column, where the bias index is clamped in ragged tiles
     if family == "walk":
         h = tsg.TCSCDevice(*arrays, K, N)
+        _pin_streams(h, M)
         assert h.call_kernel(M) == "tsg_tcsc_ell_kernel"
     else:
         h = _jit_handle(tsg, arrays, K, N, 64, 16)
@@ -433,6 +435,7 @@ def test_scaled_isolation(tsg, family):
     M, K, N = (16, 193, 301) if family == "walk" else (64, 388, 700)
     arrays, Xt, b, alpha, rs, cs, want = _scase(M, K, N, "float32", "float32")
     h = tsg.TCSCDevice(*arrays, K, N)
+    _pin_streams(h, M)
     assert h.call_kernel(M) == ("tsg_tcsc_ell_kernel" if family == "walk" else "tsg_jit64_kernel")
     Xd, bd = Xt.cuda(), _dev(b)
     launches = h.call_launches(Xd, M)
@@ -481,6 +484,7 @@ def test_scaled_graph_capture_after_reserve(tsg):
     want2 = _cast_bits(expect32(chain2, rs2, cs2, b), "bfloat16")
     assert not np.array_equal(want2, want[("both", "plain")])
     h = tsg.TCSCDevice(*arrays, K, N)
+    _pin_streams(h, M)
     assert h.call_kernel(M) == "tsg_jit64_kernel"
     h.reserve(130)
     work = h.info()["work_bytes"]

@@ -22,7 +22,7 @@ import functools
 import numpy as np
 import pytest
 
-from test_gpu_ldy import SENT, _assert_only_view_written, _bits, _case, _dev, _fill, _jit_handle
+from test_gpu_ldy import SENT, _assert_only_view_written, _bits, _case, _dev, _fill, _jit_handle, _pin_streams
 
 pytestmark = pytest.mark.gpu
 
@@ -210,6 +210,7 @@ def test_xtype_rx_kernel(tsg, monkeypatch, dtype, M, K, N):
     case = _xcase(M, K, N, dtype)
     h = tsg.TCSCDevice(*case[0], K, N)
     h.set_small_m(1)
+    _pin_streams(h, M)
     assert h.kernel_name() == "tsg_tcsc_rx_kernel" and h.call_kernel(M) == "tsg_tcsc_rx_kernel"
     check_x(h, case, ("rx", M, K, N), _offsets(K))
     h.close()
@@ -324,6 +325,7 @@ def test_xtype_isolation_bf16(tsg, family, M, K, N):
     arrays, Xt, Xw, b, alpha, ref, ref_p = case
     if family == "walk":
         h = tsg.TCSCDevice(*arrays, K, N)
+        _pin_streams(h, M)
         assert h.call_kernel(M) == "tsg_tcsc_ell_kernel"
     else:
         rows = 64 if family == "rows64" else 128
@@ -365,6 +367,7 @@ def test_xtype_work_buffer_hand_over(tsg):
     arrays_x, Xt, Xw, bx, alphax, ref_x, ref_xp = _xcase(M, K, N, "bfloat16")
     assert all(np.array_equal(a, c) for a, c in zip(arrays, arrays_x)) and np.array_equal(b, bx)
     h = tsg.TCSCDevice(*arrays, K, N)
+    _pin_streams(h, M)
     assert h.call_kernel(M) == "tsg_jit64_kernel"
     Xd, Xnd, bd = _dev(X), Xt.cuda(), _dev(b)
     assert Xd.data_ptr() % 16 == 0 and Xnd.data_ptr() % 16 == 0
@@ -399,6 +402,7 @@ def test_xtype_graph_capture_after_reserve(tsg):
     M, K, N = 64, 388, 700
     arrays, Xt, Xw, b, alpha, ref, ref_p = _xcase(M, K, N, "bfloat16")
     h = tsg.TCSCDevice(*arrays, K, N)
+    _pin_streams(h, M)
     assert h.call_kernel(M) == "tsg_jit64_kernel"
     h.reserve(130)
     work = h.info()["work_bytes"]

@@ -27,7 +27,7 @@ import functools
 import numpy as np
 import pytest
 
-from test_gpu_ldy import _bits, _case, _dev, _jit_handle
+from test_gpu_ldy import _bits, _case, _dev, _jit_handle, _pin_streams
 from test_gpu_xtype import _identity_tcsc, _tdtype
 
 pytestmark = pytest.mark.gpu
@@ -268,6 +268,7 @@ def test_ytype_rx_kernel(tsg, monkeypatch, xdtype, ydtype):
     case = _ycase(M, K, N, xdtype, ydtype)
     h = tsg.TCSCDevice(*case[0], K, N)
     h.set_small_m(1)
+    _pin_streams(h, M)
     assert h.kernel_name() == "tsg_tcsc_rx_kernel" and h.call_kernel(M) == "tsg_tcsc_rx_kernel"
     check_y(h, case, ydtype, ("rx", M, K, N, xdtype))
     h.close()
@@ -312,6 +313,7 @@ def test_ytype_direct_x_stays_one_launch(tsg):
     M, K, N = 64, 388, 700
     arrays, Xt, Xw, b, alpha, ref, ref_p, want = _ycase(M, K, N, "float32", "bfloat16")
     h = tsg.TCSCDevice(*arrays, K, N)
+    _pin_streams(h, M)
     assert h.call_kernel(M) == "tsg_jit64_kernel"
     Xd, bd = Xt.cuda(), _dev(b)
     assert Xd.data_ptr() % 16 == 0
@@ -530,6 +532,7 @@ def test_ytype_graph_capture_after_reserve(tsg):
     M, K, N = 64, 388, 700
     arrays, Xt, Xw, b, alpha, ref, ref_p, want = _ycase(M, K, N, "bfloat16", "bfloat16")
     h = tsg.TCSCDevice(*arrays, K, N)
+    _pin_streams(h, M)
     assert h.call_kernel(M) == "tsg_jit64_kernel"
     h.reserve(130)
     work = h.info()["work_bytes"]
