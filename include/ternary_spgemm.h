@@ -593,7 +593,8 @@ int tcsc_hip_reserve(tsg_tcsc *h, int max_M);
  * it -- scales, + b, PReLU, the fused epilogue, the one rounding to the Y type,
  * the written-range guarantee, drow_scale_out -- is the same code.  Any M >= 1,
  * any N, ytype, ldY.  BlockedTCSC handles, K > 131072 and calls with an fp32,
- * fp16 or bf16 X that is not quantised run as before, whatever the mode.
+ * fp16 or bf16 X that is not quantised run as before, whatever the mode (a
+ * 16-bit X has a matrix path of its own, opt-in: tcsc_hip_set_x16_mfma below).
  * mode: 0 = automatic (default): the calls it was measured to win, M >= 64
  * on a W at least a quarter nonzero and M >= 512 on one at least a sixteenth
  * nonzero; 1 = never; 2 = every eligible call; anything else
@@ -622,6 +623,52 @@ int tcsc_hip_reserve(tsg_tcsc *h, int max_M);
 int tcsc_hip_set_i8_mfma(tsg_tcsc *h, int mode);
 int tcsc_hip_call_i8_mfma(const tsg_tcsc *h, int M);
 int tcsc_hip_call_i8_kernel(const tsg_tcsc *h, int M);
+
+/* The 16-bit matrix-core kernel (tsg_x16mfma_kernel) for
+ * unquantised calls whose X is fp16 or bf16: _dev_x / _dev_xy / _dev_scaled and
+ * their PReLU twins with TSG_X_F16 or TSG_X_BF16, and tcsc_hip_gemm_dev_ex in
+ * TSG_IN_PLAIN with such an X.  Opt-in per handle, off by default, and never
+ * chosen by an automatic rule, because it does not reproduce the add streams'
+ * bytes on arbitrary X.  With the mode on, such a call on an eligible handle
+ * -- plain TCSC (CSC+packed registration included) with K <= 131072 -- and any
+ * M >= 1 runs W dense at 2 bits per entry (the image of tcsc_hip_set_i8_mfma)
+ * through v_mfma_f32_32x32x16_f16 / _bf16 with fp32 accumulators: one launch,
+ * X read in place, no work buffer.  Any N, ytype, ldY.  The contract:
+ *  - Products.  x * (+-1) and x * 0 are exact.  Each output's chain is the
+ *    fp32 sum of its column's products, accumulated by the matrix core and the
+ *    kernel in an order the library does not promise.  The order is fixed for
+ *    a given (handle, M, N, K, xtype): results are run-to-run deterministic.
+ *  - After the chain everything is the existing fp32 contract, operation for
+ *    operation: scales, + b, PReLU, the fused epilogue, the one rounding to the
+ *    Y type, the written-range guarantee, the in-place operand rule.
+ *  - Bound.  With c the nonzeros of column n, S the sum of |x[m,k]| over the k
+ *    with W[k,n] != 0 and d = c + ceil(K / 16):
+ *    |chain - exact| <= d u S / (1 - d u), u = 2^-23 -- one rounding per add,
+ *    truncation included, along any path of any summation tree.  Derived, not
+ *    measured.
+ *  - Exact case.  Where every partial sum of a chain is exactly representable
+ *    in fp32 the chain is exact, and the call stores byte for byte what it
+ *    stores with the mode off (for example an integer-valued X with
+ *    max|x| K <= 2^24).
+ *  - Special values.  A dense pass multiplies by W's zero entries: a row of X
+ *    that holds an inf or a NaN has its own row of Y unspecified (inf * 0);
+ *    nothing faults and every other row is what it is without it.  Whether
+ *    subnormal 16-bit inputs are flushed is not promised.
+ *  - Unaffected calls.  An fp32 X, an int8 X, the quantising calls and
+ *    tcsc_hip_gemm_dev_glu run as before whatever the mode, and so do
+ *    BlockedTCSC handles and K > 131072; mode 0 is the library without this
+ *    kernel, bit for bit.
+ * mode: 0 = off (default), 1 = on; anything else TSG_ERR_ARG.
+ * tcsc_hip_call_x16_mfma: 1 if an unquantised call with M rows and this xtype
+ * (a tsg_xtype) runs the kernel under the handle's current mode, else 0; a null
+ * handle is TSG_ERR_ARG.  The image is built and uploaded on the first such
+ * call; tcsc_hip_reserve does it ahead when the mode is 1, and during stream
+ * capture a call whose image is not built is TSG_ERR_ARG naming
+ * tcsc_hip_reserve.  tcsc_hip_kernel_time counts the launch.  There is no
+ * split-K variant for decode shapes yet: M <= 32 runs the same tiles.
+ * Extension: no reference counterpart. */
+int tcsc_hip_set_x16_mfma(tsg_tcsc *h, int mode);
+int tcsc_hip_call_x16_mfma(const tsg_tcsc *h, int M, int xtype);
 
 /* ---- introspection ------------------------------------------------------- */
 typedef struct tsg_info {

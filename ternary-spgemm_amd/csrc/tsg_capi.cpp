@@ -594,6 +594,28 @@ int run_i8(tsg_tcsc *h, Call &c, int kernel)
     return rc || !c.quant ? rc : work_end(h, c);
 }
 
+// An unquantised fp16 / bf16 X on the matrix cores (tsg_plan.h call_x16_mfma;
+// tsg_x16mfma.hip): X is read in place -- no work buffer, one launch, ordered
+// on the caller's stream like an int8-X call of run_i8 -- over the same image.
+int run_x16(tsg_tcsc *h, Call &c)
+{
+    const int M = c.in.M;
+    if (!h->d_i8 && c.capturing)
+        return fail(TSG_ERR_ARG, "M=" + std::to_string(M) + " runs the 16-bit matrix-core kernel, whose image is not "
+                                 "built yet; call tcsc_hip_reserve before capturing");
+    if (((int64_t)M + tsg::kX16TileM - 1) / tsg::kX16TileM * (((int64_t)h->plan.N + tsg::kX16TileN - 1) / tsg::kX16TileN) >=
+        (1ll << 31) / tsg::kX16Threads)
+        return fail(TSG_ERR_ARG, "M=" + std::to_string(M) + " is too large for one launch; split the rows");
+    int rc = ensure_i8(h);
+    if (rc) return rc;
+    int slot;
+    rc = timing_begin(h, c.capturing, c.s(), slot);
+    if (rc) return rc;
+    if (tsg::launch_tcsc_x16mfma(c.in.X, c.in.xtype, h->d_i8, h->plan.K, c.out) != 0)
+        return fail(TSG_ERR_HIP, std::string("16-bit matrix-core kernel launch: ") + hipGetErrorString(hipGetLastError()));
+    return timing_end(h, slot, c.s());
+}
+
 // The fused gate/up call (tcsc_hip_gemm_dev_glu; tsg_i8glu.hip) on the gate
 // handle h, c.out carrying the up side (the up handle's image was looked up
 // under its own lock, which is no longer held: never two handles' locks at
@@ -772,6 +794,7 @@ int run_dev(tsg_tcsc *h, Call c)
     HIP_TRY(hipStreamIsCapturing(c.s(), &cap));
     c.capturing = cap != hipStreamCaptureStatusNone;
     if (const int i8 = tsg::call_i8_kernel(h->plan, M, c.quant || c.in.xtype == tsg::kXI8)) return run_i8(h, c, i8);
+    if (tsg::call_x16_mfma(h->plan, M, c.in.xtype, c.quant)) return run_x16(h, c);
     CallPlan p = tsg::plan_call(h->plan, M);
     if (p.is_ell()) return run_ell(h, p, c);
     if (!p.is_jit()) return run_rx(h, p, c);
@@ -1291,6 +1314,11 @@ extern "C" int tcsc_hip_reserve(tsg_tcsc *h, int max_M)
         if (!rc) rc = ensure_aq(h, max_M, std::max<size_t>((size_t)std::max(max_M, 1) * h->plan.K, 16), false);
         if (rc) return rc;
     }
+    // the 16-bit matrix-core kernel reads the same image (its rule does not depend on M >= 1)
+    if (tsg::call_x16_mfma(h->plan, std::max(max_M, 1), tsg::kXBF16, false)) {
+        rc = ensure_i8(h);
+        if (rc) return rc;
+    }
     if (!h->plan.jit) return ensure_work(h, max_M, tsg::kRxTileM, tsg::kRxChunk, false);
     rc = ensure_work(h, max_M, tsg::kJitTileM, tsg::kJitChunk, false);
     // the 64-row image's k-quad X^T (same bytes or fewer)
@@ -1479,6 +1507,24 @@ extern "C" int tcsc_hip_call_i8_kernel(const tsg_tcsc *h, int M)
     if (!h || M <= 0) return 0;
     std::lock_guard<std::mutex> lk(h->mu);
     return tsg::call_i8_kernel(h->plan, M, true);
+}
+
+extern "C" int tcsc_hip_set_x16_mfma(tsg_tcsc *h, int mode)
+{
+    if (!h) return fail(TSG_ERR_ARG, "null handle");
+    if (mode < 0 || mode > 1) return fail(TSG_ERR_ARG, "tcsc_hip_set_x16_mfma: expected 0 (off) or 1 (on)");
+    std::lock_guard<std::mutex> lk(h->mu);
+    h->plan.x16_mode = mode;
+    return TSG_OK;
+}
+
+// (a null handle is TSG_ERR_ARG with its message, not a silent 0)
+extern "C" int tcsc_hip_call_x16_mfma(const tsg_tcsc *h, int M, int xtype)
+{
+    if (!h) return fail(TSG_ERR_ARG, "null handle");
+    if (M <= 0) return 0;
+    std::lock_guard<std::mutex> lk(h->mu);
+    return tsg::call_x16_mfma(h->plan, M, xtype, false);
 }
 
 extern "C" int tcsc_hip_set_i8_small(tsg_tcsc *h, int mode)

@@ -487,6 +487,17 @@ inline int i8glu_pick(int K)
 }
 int launch_tcsc_i8glu(const int8_t *X, const uint32_t *img, int K, const YOut &o, bool tile);
 
+// "x16mfma" kernel (tsg_x16mfma_kernel, tsg_x16mfma.hip): an unquantised fp16 or
+// bf16 X on the matrix cores (v_mfma_f32_32x32x16_f16 / _bf16, fp32
+// accumulators), dense over W, over the same image: a workgroup of 4 waves owns
+// 128 rows x 256 columns, a wave 128 x 64 (one granule of the image) as 4 x 2
+// accumulator tiles.  Opt-in per handle and not bit-identical to the add
+// streams on arbitrary X: tsg_plan.h call_x16_mfma.
+constexpr int kX16TileM = 128, kX16TileN = 4 * kI8WaveN;
+constexpr int kX16Threads = 256;
+// X: fp16 or bf16 [M][K] row-major, the caller's (xtype: kXF16 / kXBF16); img: the i8mfma image, uploaded
+int launch_tcsc_x16mfma(const void *X, int xtype, const uint32_t *img, int K, const YOut &o);
+
 // Environment knobs (csrc/tsg_knobs.cpp): A/B studies and tests, none of
 // which changes a result.  knob_check: "" when every set knob has an
 // accepted value, else the first error (registration and the host codegen

@@ -669,6 +669,11 @@ bool call_i8_mfma(const PlanInput &in, int M, bool int8_acts)
     return call_i8_kernel(in, M, int8_acts) != 0;
 }
 
+int call_x16_mfma(const PlanInput &in, int M, int xtype, bool quant)
+{
+    return in.x16_mode == 1 && !quant && (xtype == kXF16 || xtype == kXBF16) && i8_eligible(in) && M >= 1;
+}
+
 // Chunks of the host-pointer pipeline: one per ~16 MiB of Y (the PCIe leg
 // that binds: Y is the largest transfer), at most kHostChunksMax, each a whole
 // number of 128-row M tiles and at least 256 rows; calls the small-M kernel

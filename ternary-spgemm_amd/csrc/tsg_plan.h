@@ -40,6 +40,7 @@ struct PlanInput {
     int jit_nch = 0;            // X^T chunks of the 128-row images (all widths)
     int i8_mode = 0;            // tcsc_hip_set_i8_mfma: 0 auto, 1 never, 2 every eligible call
     int i8_small = 0;           // tcsc_hip_set_i8_small: 0 auto, 1 never the M <= 32 kernel (tsg_i8gemv.hip)
+    int x16_mode = 0;           // tcsc_hip_set_x16_mfma: 0 off, 1 every eligible fp16 / bf16 call
 };
 
 enum class Kernel { kRx, kJit128, kJit64, kEll, kEllPc };
@@ -81,6 +82,15 @@ CallPlan plan_call(const PlanInput &in, int M);
 bool i8_eligible(const PlanInput &in);
 int call_i8_kernel(const PlanInput &in, int M, bool int8_acts);
 bool call_i8_mfma(const PlanInput &in, int M, bool int8_acts);
+
+// The 16-bit matrix-core kernel (tsg_x16mfma.hip) instead of what plan_call
+// picks: 1 only when the handle opted in (x16_mode 1), the call is unquantised
+// (quant: an actquant / normquant call -- those are int8 after the input
+// stage), xtype is kXF16 or kXBF16, the handle is eligible for the image
+// (i8_eligible) and M >= 1.  Never chosen by an automatic rule: its fp32
+// accumulation is not the add streams' serial chain, so its bytes differ from
+// theirs wherever a partial sum rounds (include/ternary_spgemm.h).
+int call_x16_mfma(const PlanInput &in, int M, int xtype, bool quant);
 
 // Logical workgroup ids of a weight-compiled call: M tiles x column tiles
 // (cols = stream width x streams per workgroup)

@@ -59,6 +59,7 @@ EXPORTED_SYMBOLS = (
     "tcsc_hip_set_i8_mfma", "tcsc_hip_call_i8_mfma", "tsg_i8_build",
     "tcsc_hip_call_i8_kernel", "tcsc_hip_set_i8_small", "tsg_i8gemv_pick",
     "tcsc_hip_gemm_dev_glu", "tsg_gemm_glu_check", "tcsc_hip_reserve_glu", "tsg_i8glu_pick",
+    "tcsc_hip_set_x16_mfma", "tcsc_hip_call_x16_mfma",
 )
 
 # enum tsg_xtype (include/ternary_spgemm.h): element type of X on the _x calls
@@ -221,6 +222,8 @@ def lib() -> C.CDLL:
     L.tcsc_hip_set_i8_mfma.argtypes = [H, C.c_int]
     L.tcsc_hip_call_i8_mfma.argtypes = [H, C.c_int]
     L.tcsc_hip_call_i8_kernel.argtypes = [H, C.c_int]
+    L.tcsc_hip_set_x16_mfma.argtypes = [H, C.c_int]
+    L.tcsc_hip_call_x16_mfma.argtypes = [H, C.c_int, C.c_int]
     L.tcsc_hip_set_i8_small.argtypes = [H, C.c_int]
     L.tsg_i8gemv_pick.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.tsg_i8glu_pick.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -1303,6 +1306,18 @@ class TCSCDevice:
         the handle's current mode: 0 none, 1 tsg_i8mfma_kernel, 2
         tsg_i8gemv_kernel (M <= 32)."""
         return int(lib().tcsc_hip_call_i8_kernel(self._h, M))
+
+    def set_x16_mfma(self, mode: int) -> None:
+        """16-bit matrix-core kernel for the unquantised fp16 / bf16 calls: 0 =
+        off (default), 1 = on.  Opt-in: its fp32 accumulation order is not the
+        add streams', so Y differs from mode 0 wherever a partial sum rounds
+        (the contract: tcsc_hip_set_x16_mfma in include/ternary_spgemm.h)."""
+        _check(lib().tcsc_hip_set_x16_mfma(self._h, mode), "tcsc_hip_set_x16_mfma")
+
+    def call_x16_mfma(self, M: int, xtype: int) -> int:
+        """1 if an unquantised call with M rows and an X of `xtype` (a TSG_X_*
+        value) runs tsg_x16mfma_kernel under the handle's current mode, else 0."""
+        return int(lib().tcsc_hip_call_x16_mfma(self._h, M, xtype))
 
     def set_i8_small(self, mode: int) -> None:
         """The M <= 32 integer kernel: 0 = by the set_i8_mfma rule (default),
