@@ -39,11 +39,10 @@ def units():
             out.append((name, "tsg_jit_kernel.hip", r64 + [f"-DTSG_JIT_NW={w}", "-DTSG_JIT_WAVES=4"] + extra))
     out.append(("tsg_ell", "tsg_ell.hip", []))
     out.append(("tcsc_kernels", "tcsc_kernels.hip", []))
-    # the integer matrix-core kernels, with the Makefile's extra flags for them
+    # the matrix-core kernels, with the Makefile's extra flags for them
     nopk = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-    out.append(("tsg_i8mfma", "tsg_i8mfma.hip", nopk))
-    out.append(("tsg_i8gemv", "tsg_i8gemv.hip", nopk))
-    out.append(("tsg_i8glu", "tsg_i8glu.hip", nopk))
+    for name in ("tsg_i8mfma", "tsg_i8gemv", "tsg_i8glu", "tsg_x16mfma"):
+        out.append((name, name + ".hip", nopk))
     return out
 
 

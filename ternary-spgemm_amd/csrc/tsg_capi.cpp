@@ -503,6 +503,18 @@ int stage_begin(tsg_tcsc *h, const CallPlan &p, Call &c, bool q8)
     return TSG_OK;
 }
 
+// A quantising call on a kernel that reads X in place (the walks, the integer
+// matrix-core kernels): the row pass writes q as int8 into the scratch, and the
+// kernel runs on it as an int8-X call scaled by the scratch's deq (no X^T, so
+// no plan: work_begin's q8 case)
+int quantise_to_i8(tsg_tcsc *h, Call &c)
+{
+    const int rc = stage_begin(h, CallPlan{}, c, true);
+    if (rc) return rc;
+    c.in.X = h->d_aq8, c.in.xtype = tsg::kXI8;
+    return TSG_OK;
+}
+
 // small M: the ELL walk reads X in place, whatever its element type (no X^T
 // staging, no work buffer)
 int run_ell(tsg_tcsc *h, const CallPlan &p, Call &c)
@@ -512,13 +524,7 @@ int run_ell(tsg_tcsc *h, const CallPlan &p, Call &c)
                                  "built yet; call tcsc_hip_reserve before capturing");
     int rc = ensure_ell(h, p.ell);
     if (rc) return rc;
-    // an actquant call: the row pass writes q as int8 into the scratch, and the
-    // walk runs on it as an int8-X call scaled by the scratch's deq
-    if (c.quant) {
-        rc = stage_begin(h, p, c, true);
-        if (rc) return rc;
-        c.in.X = h->d_aq8, c.in.xtype = tsg::kXI8;
-    }
+    if (c.quant && (rc = quantise_to_i8(h, c))) return rc;
     int slot;
     rc = timing_begin(h, c.capturing, c.s(), slot);
     if (rc) return rc;
@@ -557,94 +563,65 @@ int ensure_i8(tsg_tcsc *h)
     return TSG_OK;
 }
 
-// int8 activations on the integer matrix cores (tsg_plan.h call_i8_mfma): an
-// int8 X is read in place -- no work buffer, one launch; a quantising call's
-// row pass writes q as int8 into the scratch and the kernel runs on it as an
-// int8-X call scaled by the scratch's deq, as the walks do.  `kernel`
-// (tsg_plan.h call_i8_kernel): 1 the 128 x 128 tiles, 2 the M <= 32 split-K
-// kernel; both read the one image.
-int run_i8(tsg_tcsc *h, Call &c, int kernel)
+// The calls on the matrix cores, over the one packed image: X is read in place
+// -- no work buffer, one launch, ordered on the caller's stream; a quantising
+// call's row pass writes q as int8 into the scratch first (quantise_to_i8).
+//   kI8Tile, kI8SplitK  int8 activations (tsg_plan.h call_i8_kernel: the
+//                       128 x 128 tiles, the M <= 32 split-K kernel)
+//   kX16                an unquantised fp16 / bf16 X (tsg_plan.h call_x16_mfma)
+//   kGlu                the fused gate/up call (tcsc_hip_gemm_dev_glu) on the
+//                       gate handle h, c.out carrying the up side (the up
+//                       handle's image was looked up under its own lock, which
+//                       is no longer held: never two handles' locks at once);
+//                       the scratch, the timing and the work event are the gate
+//                       handle's.  Always the integer kernels, whatever i8_mode
+//                       says; i8_small sends M <= 32 to the tile variant too.
+enum class Mfma { kI8Tile, kI8SplitK, kX16, kGlu };
+struct MfmaKind {
+    // the grid mfma_grid_ok bounds: the tile kernel's, which the split-K and GLU grids are at most twice
+    int tile_m, tile_n, threads;
+    const char *name;             // in the capture refusal and in front of " launch: "
+};
+constexpr MfmaKind kMfmaKinds[] = {
+    {tsg::kI8TileM, tsg::kI8TileN, tsg::kI8Threads, "int8 matrix-core kernel"},
+    {tsg::kI8TileM, tsg::kI8TileN, tsg::kI8Threads, "int8 matrix-core kernel"},
+    {tsg::kX16TileM, tsg::kX16TileN, tsg::kX16Threads, "16-bit matrix-core kernel"},
+    {tsg::kI8TileM, tsg::kI8TileN, tsg::kI8Threads, "fused gate/up kernel"},
+};
+
+int run_mfma(tsg_tcsc *h, Call &c, Mfma kind)
 {
-    const int M = c.in.M;
-    // a captured call that cannot run is refused before anything is enqueued:
-    // the scratch first (the message of the other quantising paths), then the image
-    if (c.capturing && c.quant)
-        if (const int rq = ensure_aq(h, M, std::max<size_t>((size_t)M * h->plan.K, 16), true)) return rq;
-    if (!h->d_i8 && c.capturing)
-        return fail(TSG_ERR_ARG, "M=" + std::to_string(M) + " runs the int8 matrix-core kernel, whose image is not "
-                                 "built yet; call tcsc_hip_reserve before capturing");
-    if (((int64_t)M + tsg::kI8TileM - 1) / tsg::kI8TileM * (((int64_t)h->plan.N + tsg::kI8TileN - 1) / tsg::kI8TileN) >=
-        (1ll << 31) / 256)
+    const MfmaKind &k = kMfmaKinds[(int)kind];
+    const int M = c.in.M, K = h->plan.K;
+    const size_t q8 = std::max<size_t>((size_t)M * K, 16);
+    // a captured call that cannot run is refused before anything is enqueued
+    if (c.capturing && kind == Mfma::kGlu) {
+        if ((c.quant && (((size_t)M + 127) / 128 * 128 > h->aq_rows || q8 > h->aq8_bytes)) || !h->d_i8)
+            return fail(TSG_ERR_ARG, "M=" + std::to_string(M) + " needs the gate handle's int8 matrix-core image and "
+                                     "quantisation scratch, which are not ready during stream capture; call "
+                                     "tcsc_hip_reserve_glu(h_gate, h_up, max_M) before capturing");
+    } else if (c.capturing) {
+        // the scratch first (the message of the other quantising paths), then the image
+        if (c.quant)
+            if (const int rq = ensure_aq(h, M, q8, true)) return rq;
+        if (!h->d_i8)
+            return fail(TSG_ERR_ARG, "M=" + std::to_string(M) + " runs the " + k.name + ", whose image is not "
+                                     "built yet; call tcsc_hip_reserve before capturing");
+    }
+    if (!tsg::mfma_grid_ok(M, h->plan.N, k.tile_m, k.tile_n, k.threads))
         return fail(TSG_ERR_ARG, "M=" + std::to_string(M) + " is too large for one launch; split the rows");
     int rc = ensure_i8(h);
     if (rc) return rc;
-    if (c.quant) {
-        rc = stage_begin(h, CallPlan{}, c, true);
-        if (rc) return rc;
-        c.in.X = h->d_aq8, c.in.xtype = tsg::kXI8;
-    }
+    if (c.quant && (rc = quantise_to_i8(h, c))) return rc;
     int slot;
     rc = timing_begin(h, c.capturing, c.s(), slot);
     if (rc) return rc;
     const int8_t *X8 = static_cast<const int8_t *>(c.in.X);
-    if ((kernel == 2 ? tsg::launch_tcsc_i8gemv(X8, h->d_i8, h->plan.K, c.out)
-                     : tsg::launch_tcsc_i8mfma(X8, h->d_i8, h->plan.K, c.out)) != 0)
-        return fail(TSG_ERR_HIP, std::string("int8 matrix-core kernel launch: ") + hipGetErrorString(hipGetLastError()));
-    rc = timing_end(h, slot, c.s());
-    return rc || !c.quant ? rc : work_end(h, c);
-}
-
-// An unquantised fp16 / bf16 X on the matrix cores (tsg_plan.h call_x16_mfma;
-// tsg_x16mfma.hip): X is read in place -- no work buffer, one launch, ordered
-// on the caller's stream like an int8-X call of run_i8 -- over the same image.
-int run_x16(tsg_tcsc *h, Call &c)
-{
-    const int M = c.in.M;
-    if (!h->d_i8 && c.capturing)
-        return fail(TSG_ERR_ARG, "M=" + std::to_string(M) + " runs the 16-bit matrix-core kernel, whose image is not "
-                                 "built yet; call tcsc_hip_reserve before capturing");
-    if (((int64_t)M + tsg::kX16TileM - 1) / tsg::kX16TileM * (((int64_t)h->plan.N + tsg::kX16TileN - 1) / tsg::kX16TileN) >=
-        (1ll << 31) / tsg::kX16Threads)
-        return fail(TSG_ERR_ARG, "M=" + std::to_string(M) + " is too large for one launch; split the rows");
-    int rc = ensure_i8(h);
-    if (rc) return rc;
-    int slot;
-    rc = timing_begin(h, c.capturing, c.s(), slot);
-    if (rc) return rc;
-    if (tsg::launch_tcsc_x16mfma(c.in.X, c.in.xtype, h->d_i8, h->plan.K, c.out) != 0)
-        return fail(TSG_ERR_HIP, std::string("16-bit matrix-core kernel launch: ") + hipGetErrorString(hipGetLastError()));
-    return timing_end(h, slot, c.s());
-}
-
-// The fused gate/up call (tcsc_hip_gemm_dev_glu; tsg_i8glu.hip) on the gate
-// handle h, c.out carrying the up side (the up handle's image was looked up
-// under its own lock, which is no longer held: never two handles' locks at
-// once).  run_i8 with two images: the scratch, the timing and the work event
-// are the gate handle's.  Always the integer kernels, whatever i8_mode says;
-// i8_small sends M <= 32 to the tile variant too.
-int run_glu(tsg_tcsc *h, Call &c)
-{
-    const int M = c.in.M;
-    const size_t q8 = std::max<size_t>((size_t)M * h->plan.K, 16);
-    if (c.capturing && ((c.quant && (((size_t)M + 127) / 128 * 128 > h->aq_rows || q8 > h->aq8_bytes)) || !h->d_i8))
-        return fail(TSG_ERR_ARG, "M=" + std::to_string(M) + " needs the gate handle's int8 matrix-core image and "
-                                 "quantisation scratch, which are not ready during stream capture; call "
-                                 "tcsc_hip_reserve_glu(h_gate, h_up, max_M) before capturing");
-    if (((int64_t)M + tsg::kI8TileM - 1) / tsg::kI8TileM * (((int64_t)h->plan.N + tsg::kI8TileN - 1) / tsg::kI8TileN) >=
-        (1ll << 31) / 256)
-        return fail(TSG_ERR_ARG, "M=" + std::to_string(M) + " is too large for one launch; split the rows");
-    int rc = ensure_i8(h);
-    if (rc) return rc;
-    if (c.quant) {
-        rc = stage_begin(h, CallPlan{}, c, true);
-        if (rc) return rc;
-        c.in.X = h->d_aq8, c.in.xtype = tsg::kXI8;
-    }
-    int slot;
-    rc = timing_begin(h, c.capturing, c.s(), slot);
-    if (rc) return rc;
-    if (tsg::launch_tcsc_i8glu(static_cast<const int8_t *>(c.in.X), h->d_i8, h->plan.K, c.out, h->plan.i8_small == 1) != 0)
-        return fail(TSG_ERR_HIP, std::string("fused gate/up kernel launch: ") + hipGetErrorString(hipGetLastError()));
+    const int lrc = kind == Mfma::kI8Tile     ? tsg::launch_tcsc_i8mfma(X8, h->d_i8, K, c.out)
+                    : kind == Mfma::kI8SplitK ? tsg::launch_tcsc_i8gemv(X8, h->d_i8, K, c.out)
+                    : kind == Mfma::kX16      ? tsg::launch_tcsc_x16mfma(c.in.X, c.in.xtype, h->d_i8, K, c.out)
+                                              : tsg::launch_tcsc_i8glu(X8, h->d_i8, K, c.out, h->plan.i8_small == 1);
+    if (lrc != 0) return fail(TSG_ERR_HIP, std::string(k.name) + " launch: " + hipGetErrorString(hipGetLastError()));
     rc = timing_end(h, slot, c.s());
     return rc || !c.quant ? rc : work_end(h, c);
 }
@@ -793,8 +770,9 @@ int run_dev(tsg_tcsc *h, Call c)
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     HIP_TRY(hipStreamIsCapturing(c.s(), &cap));
     c.capturing = cap != hipStreamCaptureStatusNone;
-    if (const int i8 = tsg::call_i8_kernel(h->plan, M, c.quant || c.in.xtype == tsg::kXI8)) return run_i8(h, c, i8);
-    if (tsg::call_x16_mfma(h->plan, M, c.in.xtype, c.quant)) return run_x16(h, c);
+    if (const int i8 = tsg::call_i8_kernel(h->plan, M, c.quant || c.in.xtype == tsg::kXI8))
+        return run_mfma(h, c, i8 == 2 ? Mfma::kI8SplitK : Mfma::kI8Tile);
+    if (tsg::call_x16_mfma(h->plan, M, c.in.xtype, c.quant)) return run_mfma(h, c, Mfma::kX16);
     CallPlan p = tsg::plan_call(h->plan, M);
     if (p.is_ell()) return run_ell(h, p, c);
     if (!p.is_jit()) return run_rx(h, p, c);
@@ -1927,7 +1905,7 @@ extern "C" int tcsc_hip_gemm_dev_glu(tsg_tcsc *h_gate, tsg_tcsc *h_up, const tsg
         c.out.img_up = h_up->d_i8;
     }
     std::lock_guard<std::mutex> lk(h_gate->mu);
-    return run_glu(h_gate, c);
+    return run_mfma(h_gate, c, Mfma::kGlu);
 }
 
 extern "C" int tcsc_hip_reserve_glu(tsg_tcsc *h_gate, tsg_tcsc *h_up, int max_M)

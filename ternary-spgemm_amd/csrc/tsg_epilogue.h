@@ -16,6 +16,7 @@
 #include <cstdint>
 
 #include "tsg_internal.h"
+#include "tsg_scale.h"
 #include "tsg_ytype.h"
 
 namespace tsg {
@@ -116,6 +117,30 @@ __device__ __forceinline__ void epi_store1(void *Y, int yt, int64_t ldY, const E
         r = epi_load1(epi_base(ep.add, ep.bits & kEpiAddIsY, Y), (ep.bits >> kEpiAddShift) & 3,
                       (size_t)m * (size_t)ep.ldadd + n);
     ystore1_any(Y, yt, (size_t)m * (size_t)ldY + n, epi_apply(y, ep.bits & kEpiActMask, has_mul, g, has_add, r));
+}
+
+// One element a lane holds, from the finished fp32 value v to memory: through
+// the fused epilogue when the call has one (epi: the launcher's kYEpi flag,
+// wave-uniform), else the plain store
+__device__ __forceinline__ void store1(void *Y, int yt, bool epi, int64_t ldY, const Epi &ep, int m, int n, float v)
+{
+    if (epi)
+        epi_store1(Y, yt, ldY, ep, m, n, v);
+    else
+        ystore1_any(Y, yt, (size_t)m * (size_t)ldY + n, v);
+}
+
+// The per-element finish of a kernel with one element per lane (the
+// matrix-core kernels): the chain's value through scale_bias (tsg_scale.h; rm,
+// cn: the row's and the column's scale where the call has one), the PReLU
+// (an = alpha[n]; comp_prelu.h:57-67), then store1
+template <bool PRELU>
+__device__ __forceinline__ void finish_store1(void *Y, int yt, bool epi, int64_t ldY, const Epi &ep, int m, int n,
+                                              float chain, bool has_rs, float rm, bool has_cs, float cn, float bn, float an)
+{
+    float v = scale_bias(chain, has_rs, rm, has_cs, cn, bn);
+    if (PRELU) v = (v > 0) ? v : an * v;
+    store1(Y, yt, epi, ldY, ep, m, n, v);
 }
 
 // NW consecutive values of a lane's row segment through the epilogue (the

@@ -19,20 +19,18 @@
 // concurrent B loads are one contiguous run of the image.  No workgroup shares
 // an output with another: no atomics, no workspace.  With TN = 32 the two
 // halves of a 64-column granule are separate workgroups reading alternate 8
-// bytes of the same lines, so the grid is numbered to put them on one XCD (ids
-// b and b + 8: workgroups go round the 8 XCDs by id, tsg_jit_map.h) and its L2.
+// bytes of the same lines, so the grid is numbered to put them on one XCD and
+// its L2 (tsg_i8frag.h i8_splitk_tile).
 //
 // B (weights).  Per step a lane's 16 bytes (TN = 64) or its contiguous 8 bytes
 // of column half c2 (TN = 32: dwords 2 c2 and 2 c2 + 1) are one load, global
 // memory to registers, unpacked there by i8_unpack (tsg_i8frag.h).
 //
 // A (activations).  No wave reads a k range another wave of its workgroup
-// reads, so X is not staged in LDS: lane l loads its fragment of k half kk --
-// row l % 32, the 16 bytes at k = 64 ks + 32 kk + 16 (l / 32) -- from global
-// memory (X is at most 32 K bytes, in L2 for every workgroup after the
-// first): one 16-byte load where K % 16 == 0 and X is 16-byte aligned, else
-// byte by byte; rows >= M and k >= K are zero and nothing outside
-// [X, X + M K) is read.
+// reads, so X is not staged in LDS: a lane loads its two fragments of a step
+// from global memory (tsg_i8frag.h i8_afrag_pair, by the read rule of
+// i8_apiece; X is at most 32 K bytes, in L2 for every workgroup after the
+// first).
 //
 // Latency.  kI8GemvDepth steps of A and B are in flight in registers before
 // the first matrix instruction, and a slot is reloaded as soon as it is
@@ -43,10 +41,9 @@
 // Reduce and store.  Each wave sums its k halves and writes its accumulator
 // registers to LDS as [wave][register][lane] ints -- a register's 64 lanes are
 // 64 consecutive dwords: conflict-free -- one barrier, then wave w takes the
-// registers w, w + S, ... (a register is a row group: lanes 0-31 the 32 columns
-// of row 8 (r / 4) + r % 4, lanes 32-63 those of the row 4 below), sums their S
-// partials, converts, and runs tsg_i8mfma_kernel's epilogue through the same
-// helpers, one element per lane.  Registers whose rows are all >= M are
+// registers w, w + S, ... (a register is a row group: tsg_i8frag.h mfma_row),
+// sums their S partials, converts, and finishes the element it holds through
+// finish_store1 (tsg_epilogue.h).  Registers whose rows are all >= M are
 // neither written nor read.
 #include <hip/hip_runtime.h>
 
@@ -55,7 +52,6 @@
 #include "tsg_epilogue.h"
 #include "tsg_i8frag.h"
 #include "tsg_internal.h"
-#include "tsg_scale.h"
 #include "tsg_ytype.h"
 
 namespace tsg {
@@ -85,19 +81,14 @@ __global__ __launch_bounds__(TN == 64 ? 64 * kI8GemvWaves64 : 64 * kI8GemvWaves3
     const int lane = threadIdx.x & 63, S = (int)(blockDim.x >> 6);
     const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     // the workgroup's tile: granule ct of 64 columns, and of it column half `half` (TN = 32)
-    int ct = (int)blockIdx.x, half = 0;
-    if (TN == 32) {
-        const int idx = (int)blockIdx.x >> 3;
-        ct = (idx >> 1) * 8 + ((int)blockIdx.x & 7);
-        half = idx & 1;
-    }
-    const int n0 = kI8WaveN * ct + 32 * half;
+    const I8SplitKTile t = TN == 32 ? i8_splitk_tile((int)blockIdx.x) : I8SplitKTile{(int)blockIdx.x, 0};
+    const int ct = t.ct, half = t.half, n0 = kI8WaveN * ct + 32 * half;
     if (n0 >= N) return;  // (uniform) a workgroup of the grid's padding to 16
 
     const uint32_t *bw = img + ((size_t)ct * nks * 64 + lane) * 4 + 2 * half;  // step ks at bw + 256 ks
     const int row = lane & 31, kl = 16 * (lane >> 5);
-    const int8_t *xr = X + (size_t)(row < M ? row : 0) * K;
-    const int cnt = nks > w ? (nks - w + S - 1) / S : 0;  // the wave's steps
+    const int8_t *xr = i8_arow(X, row, M, K);
+    const int cnt = i8_wave_steps(nks, w, S);
 
     uint32_t bq[D][2 * C2];
     v4i a[D][2];
@@ -113,24 +104,9 @@ __global__ __launch_bounds__(TN == 64 ? 64 * kI8GemvWaves64 : 64 * kI8GemvWaves3
                 const uint2 v = *reinterpret_cast<const uint2 *>(p);
                 bq[d][0] = v.x, bq[d][1] = v.y;
             }
-#pragma unroll
-            for (int kk = 0; kk < 2; kk++) {
-                const int k = ks * kI8KStep + 32 * kk + kl;
-                if (xvec) {  // K % 16 == 0: a piece is inside a row or past its end
-                    const bool in = row < M && k < K;
-                    const v4i v = *reinterpret_cast<const v4i *>(xr + (in ? k : 0));
-                    a[d][kk] = in ? v : v4i{0, 0, 0, 0};
-                } else {
-                    uint32_t x[4] = {0, 0, 0, 0};
-                    if (row < M)
-                        for (int e = 0; e < 16 && k + e < K; e++)
-                            x[e >> 2] |= (uint32_t)(uint8_t)xr[k + e] << (8 * (e & 3));
-                    a[d][kk] = v4i{(int)x[0], (int)x[1], (int)x[2], (int)x[3]};
-                }
-            }
+            i8_afrag_pair(xr, row < M, kl, ks, K, xvec, a[d]);
         } else {
-#pragma unroll
-            for (int kk = 0; kk < 2; kk++) a[d][kk] = v4i{0, 0, 0, 0};
+            i8_afrag_zero(a[d]);
         }
     };
 
@@ -160,28 +136,24 @@ __global__ __launch_bounds__(TN == 64 ? 64 * kI8GemvWaves64 : 64 * kI8GemvWaves3
         }
     }
 
-    // register j = 16 c2 + r of the wave -> red[(w NR + j) 64 + lane]; its first row is 8 (r / 4) + r % 4
+    // register j = 16 c2 + r of the wave -> red[(w NR + j) 64 + lane]
 #pragma unroll
     for (int c2 = 0; c2 < C2; c2++)
 #pragma unroll
         for (int r = 0; r < 16; r++)
-            if (8 * (r >> 2) + (r & 3) < M) red[(w * NR + 16 * c2 + r) * 64 + lane] = acc[c2][0][r] + acc[c2][1][r];
+            if (mfma_row0(r) < M) red[(w * NR + 16 * c2 + r) * 64 + lane] = acc[c2][0][r] + acc[c2][1][r];
     __syncthreads();
 
     const int yt = ytype & kYTypeMask;
     const bool has_rs = rs != nullptr, has_cs = cs != nullptr, epi = (ytype & kYEpi) != 0;
     for (int j = w; j < NR; j += S) {
-        const int r = j & 15, m = 8 * (r >> 2) + 4 * (lane >> 5) + (r & 3), n = n0 + 32 * (j >> 4) + (lane & 31);
-        if (8 * (r >> 2) + (r & 3) >= M) continue;  // (uniform) a register of padding rows
+        const int r = j & 15, m = mfma_row(r, lane), n = n0 + 32 * (j >> 4) + (lane & 31);
+        if (mfma_row0(r) >= M) continue;  // (uniform) a register of padding rows
         int sum = 0;
         for (int s = 0; s < S; s++) sum += red[(s * NR + j) * 64 + lane];
         if (m >= M || n >= N) continue;
-        float v = scale_bias((float)sum, has_rs, has_rs ? rs[m] : 0.0f, has_cs, has_cs ? cs[n] : 0.0f, b[n]);
-        if (PRELU) v = (v > 0) ? v : alpha[n] * v;  // comp_prelu.h:57-67
-        if (epi)  // a fused epilogue (uniform: the launcher's flag; tsg_epilogue.h)
-            epi_store1(Y, yt, ldY, ep, m, n, v);
-        else
-            ystore1_any(Y, yt, (size_t)m * (size_t)ldY + n, v);
+        finish_store1<PRELU>(Y, yt, epi, ldY, ep, m, n, (float)sum, has_rs, has_rs ? rs[m] : 0.0f, has_cs,
+                             has_cs ? cs[n] : 0.0f, b[n], PRELU ? alpha[n] : 0.0f);
     }
 }
 
@@ -189,8 +161,6 @@ int launch_tcsc_i8gemv(const int8_t *X, const uint32_t *img, int K, const YOut &
 {
     if (o.M < 1 || o.M > kI8GemvMaxM) return -2;  // (the plan sends no other call here)
     const I8GemvPick p = i8gemv_pick(K, o.N);
-    const int nks = (K + kI8KStep - 1) / kI8KStep;
-    const int xvec = K > 0 && K % 16 == 0 && ((uintptr_t)X & 15) == 0;
     // TN = 64: one workgroup per granule; TN = 32: two, the granules padded to
     // a multiple of 8 (the XCD numbering above; the padding returns at once)
     const int64_t granules = ((int64_t)o.N + kI8WaveN - 1) / kI8WaveN;
@@ -200,7 +170,7 @@ int launch_tcsc_i8gemv(const int8_t *X, const uint32_t *img, int K, const YOut &
     auto *kernel = p.tn == 64 ? (o.prelu ? tsg_i8gemv_kernel<64, true> : tsg_i8gemv_kernel<64, false>)
                               : (o.prelu ? tsg_i8gemv_kernel<32, true> : tsg_i8gemv_kernel<32, false>);
     hipLaunchKernelGGL(kernel, grid, block, lds, (hipStream_t)o.stream, X, img, o.b, o.alpha, o.rs, o.cs, o.ep,
-                       static_cast<float *>(o.Y), o.ldY, o.kernel_ytype(false), o.M, o.N, K, nks, xvec);
+                       static_cast<float *>(o.Y), o.ldY, o.kernel_ytype(false), o.M, o.N, K, i8_nks(K), x_vec_ok(X, K, 16));
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

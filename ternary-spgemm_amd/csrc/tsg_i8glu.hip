@@ -17,28 +17,27 @@
 // columns, one granule of either image.  Wave (wm, wn) owns rows 64 wm .. + 63
 // and the 32 columns of column half wn, for BOTH matrices: acc[row tile][matrix]
 // is 64 accumulator registers, tsg_i8mfma_kernel's budget, so two workgroups
-// still share a CU.  A: that kernel's staging to the letter (128 x 64 bytes,
-// global -> registers -> a double-buffered LDS tile of 80-byte pitch, the
-// 16-byte / byte-wise rule, zeros past M and K, nothing outside [X, X + M K)
-// read, one barrier per step).  B: per step a lane loads its contiguous 8
-// bytes of column half wn (dwords 2 wn and 2 wn + 1) from each image, one step
-// ahead, registers only.  Per step a wave issues 4 ds_read_b128, 4 unpacks and
-// 8 matrix instructions: an A fragment feeds both matrices, a B fragment both
-// row tiles -- tsg_i8mfma_kernel's ratio.  Grid: one workgroup per (M tile,
-// granule), the granule fastest: twice tsg_i8mfma_kernel's workgroups per call.
+// still share a CU.  A: the double-buffered LDS tile both tile kernels take
+// from tsg_i8frag.h (loaded through i8_apiece), one barrier per step.  B: per
+// step a lane loads its contiguous 8 bytes of column half wn (dwords 2 wn and
+// 2 wn + 1) from each image, one step ahead, registers only.  Per step a wave
+// issues 4 ds_read_b128, 4 unpacks and 8 matrix instructions: an A fragment
+// feeds both matrices, a B fragment both row tiles -- tsg_i8mfma_kernel's
+// ratio.  Grid: one workgroup per (M tile, granule), the granule fastest:
+// twice tsg_i8mfma_kernel's workgroups per call.
 //
 // Split-K variant.  One workgroup per 32 output columns, S waves (1, 2, 4, 8:
 // tsg_internal.h i8glu_pick) taking the k-steps w, w + S, ...; a wave holds
 // acc[matrix][k half] = 64 registers and loads per step 8 bytes of each image
-// and its two A fragments straight from global memory, tsg_i8gemv_kernel's
-// depth-2 register pipeline with a zero A past the wave's last step: no LDS
-// and no barrier in the K loop.  The grid is that kernel's TN = 32 numbering
-// (the two halves of a granule on one XCD, granules padded to a multiple of 8,
-// padding workgroups return at once).  Reduce: registers 0-15 are gate, 16-31
-// up, [S][32][64] ints of LDS (8 KiB S); after the one barrier wave w takes
-// r = w, w + S, ... of 16 and sums the S partials of registers r AND 16 + r,
-// so y and u of an element meet in one lane.  Registers whose rows are all
-// >= M are neither written nor read.
+// and its two A fragments straight from global memory (tsg_i8frag.h
+// i8_afrag_pair), kGluDepth steps in flight in registers with a zero A past the
+// wave's last step: no LDS and no barrier in the K loop.  The grid is the
+// split-K numbering of tsg_i8frag.h (i8_splitk_tile: the two halves of a
+// granule on one XCD).  Reduce: registers 0-15 are gate, 16-31 up, [S][32][64]
+// ints of LDS (8 KiB S); after the one barrier wave w takes r = w, w + S, ...
+// of 16 and sums the S partials of registers r AND 16 + r, so y and u of an
+// element meet in one lane (tsg_i8frag.h mfma_row).  Registers whose rows are
+// all >= M are neither written nor read.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -46,16 +45,13 @@
 #include "tsg_epilogue.h"
 #include "tsg_i8frag.h"
 #include "tsg_internal.h"
-#include "tsg_scale.h"
 #include "tsg_ytype.h"
 
 namespace tsg {
 
 namespace {
 
-constexpr int kGluPitch = kI8KStep + 16;  // LDS bytes per row (tsg_i8mfma.hip: the bank argument)
-constexpr int kGluThreads = 256;
-constexpr int kGluDepth = 2;              // steps in flight per wave of the split-K variant (tsg_i8gemv.hip)
+constexpr int kGluDepth = 2;  // steps in flight per wave of the split-K variant (tsg_i8gemv.hip: the measurement)
 
 // What both variants hand their epilogue; by value, one kernel argument
 struct GluOut {
@@ -99,23 +95,19 @@ __device__ __forceinline__ void glu_store1(float *Y, const GluOut &o, const GluC
         if (o.act == kEpiRelu2) a = a * a;
     }
     a = a * u;
-    const int yt = o.ytype & kYTypeMask;
-    if (o.ytype & kYEpi)  // (uniform) the caller's dmul / dadd
-        epi_store1(Y, yt, o.ldY, o.ep, m, n, a);
-    else
-        ystore1_any(Y, yt, (size_t)m * (size_t)o.ldY + n, a);
+    store1(Y, o.ytype & kYTypeMask, (o.ytype & kYEpi) != 0, o.ldY, o.ep, m, n, a);  // the caller's dmul / dadd
 }
 
 }  // namespace
 
 template <bool PRELU>
-__global__ __launch_bounds__(kGluThreads, 2) void tsg_i8glu_kernel(const int8_t *__restrict__ X,
+__global__ __launch_bounds__(kI8Threads, 2) void tsg_i8glu_kernel(const int8_t *__restrict__ X,
                                                                    const uint32_t *__restrict__ img_g,
                                                                    const uint32_t *__restrict__ img_u, GluOut o,
                                                                    float *__restrict__ Y, int M, int N, int K, int nks,
                                                                    int granules, int xvec)
 {
-    __shared__ __attribute__((aligned(16))) uint8_t xs[2][kI8TileM * kGluPitch];
+    __shared__ __attribute__((aligned(16))) uint8_t xs[2][kI8TileM * kI8Pitch];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
     const int ct = blockIdx.x % granules, mt = blockIdx.x / granules;
@@ -126,12 +118,22 @@ __global__ __launch_bounds__(kGluThreads, 2) void tsg_i8glu_kernel(const int8_t 
     const size_t boff = ((size_t)ct * nks * 64 + lane) * 4 + 2 * wn;
     const uint32_t *bg = img_g + boff, *bu = img_u + boff;
 
-    // the thread's two pieces of a step's A tile, global -> registers ...
+    v16i acc[2][2];  // [row tile][matrix: 0 gate, 1 up]
+#pragma unroll
+    for (int rt = 0; rt < 2; rt++)
+#pragma unroll
+        for (int mx = 0; mx < 2; mx++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) acc[rt][mx][r] = 0;
+
+    // the thread's two pieces of a step's A tile, global -> registers: i8_apiece's
+    // rule (tsg_i8frag.h) written out -- through the helper this kernel's M = 64
+    // cells ran 1.0-1.3 % slower, past their spread (profiles/mfma_shared_ab.jsonl)
     uint4 areg[2];
     auto aload = [&](int ks) {
 #pragma unroll
         for (int j = 0; j < 2; j++) {
-            const int p = tid + kGluThreads * j, m = m0 + (p >> 2), k = ks * kI8KStep + 16 * (p & 3);
+            const int p = tid + kI8Threads * j, m = m0 + (p >> 2), k = ks * kI8KStep + 16 * (p & 3);
             if (xvec) {  // K % 16 == 0: a piece is inside a row or past its end
                 const bool in = m < M && k < K;
                 const uint4 v = *reinterpret_cast<const uint4 *>(X + (in ? (size_t)m * K + k : 0));
@@ -145,45 +147,23 @@ __global__ __launch_bounds__(kGluThreads, 2) void tsg_i8glu_kernel(const int8_t 
             }
         }
     };
-    // ... -> the LDS tile `buf`
-    auto astore = [&](int buf) {
-#pragma unroll
-        for (int j = 0; j < 2; j++) {
-            const int p = tid + kGluThreads * j;
-            *reinterpret_cast<uint4 *>(&xs[buf][(p >> 2) * kGluPitch + 16 * (p & 3)]) = areg[j];
-        }
-    };
-
-    v16i acc[2][2];  // [row tile][matrix: 0 gate, 1 up]
-#pragma unroll
-    for (int rt = 0; rt < 2; rt++)
-#pragma unroll
-        for (int mx = 0; mx < 2; mx++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) acc[rt][mx][r] = 0;
-
     uint2 qg = make_uint2(0, 0), qu = make_uint2(0, 0);
     if (nks > 0) {
         qg = *reinterpret_cast<const uint2 *>(bg);
         qu = *reinterpret_cast<const uint2 *>(bu);
         aload(0);
-        astore(0);
+        i8_atile_store(xs[0], areg);
     }
     __syncthreads();
-    const int arow = (64 * wm + (lane & 31)) * kGluPitch + 16 * (lane >> 5);
+    const int arow = i8_afrag_offset(64 * wm, lane);
     for (int ks = 0; ks < nks; ks++) {
         const bool more = ks + 1 < nks;
         const size_t nxt = (size_t)(more ? ks + 1 : ks) * 256;  // the next step's B, in flight over this one
         const uint2 ng = *reinterpret_cast<const uint2 *>(bg + nxt), nu = *reinterpret_cast<const uint2 *>(bu + nxt);
         if (more) aload(ks + 1);
         if (live) {
-            const uint8_t *xb = xs[ks & 1] + arow;
             v4i a[2][2];
-#pragma unroll
-            for (int rt = 0; rt < 2; rt++)
-#pragma unroll
-                for (int kk = 0; kk < 2; kk++)
-                    a[rt][kk] = *reinterpret_cast<const v4i *>(xb + 32 * rt * kGluPitch + 32 * kk);
+            i8_afrags(xs[ks & 1] + arow, a);
             const uint32_t bword[2][2] = {{qg.x, qg.y}, {qu.x, qu.y}};
 #pragma unroll
             for (int mx = 0; mx < 2; mx++)
@@ -195,14 +175,12 @@ __global__ __launch_bounds__(kGluThreads, 2) void tsg_i8glu_kernel(const int8_t 
                         acc[rt][mx] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[rt][kk], bf, acc[rt][mx], 0, 0, 0);
                 }
         }
-        if (more) astore((ks + 1) & 1);
+        if (more) i8_atile_store(xs[(ks + 1) & 1], areg);
         qg = ng, qu = nu;
         __syncthreads();  // the next tile is written; this one's reads are done
     }
     if (!live) return;
 
-    // Accumulator register r of a 32 x 32 tile: lanes 0-31 hold the 32 columns
-    // of row 8 (r / 4) + r % 4, lanes 32-63 those of the row 4 below
     const int n = nw + (lane & 31);
     if (n >= N) return;
     const GluCol c = glu_col<PRELU>(o, n);
@@ -210,7 +188,7 @@ __global__ __launch_bounds__(kGluThreads, 2) void tsg_i8glu_kernel(const int8_t 
     for (int rt = 0; rt < 2; rt++)
 #pragma unroll
         for (int r = 0; r < 16; r++) {
-            const int m = mw + 32 * rt + 8 * (r >> 2) + 4 * (lane >> 5) + (r & 3);
+            const int m = mw + 32 * rt + mfma_row(r, lane);
             if (m < M) glu_store1<PRELU>(Y, o, c, acc[rt][0][r], acc[rt][1][r], m, n);
         }
 }
@@ -226,17 +204,16 @@ __global__ __launch_bounds__(64 * kI8GluWaves) void tsg_i8glu_gemv_kernel(const 
     constexpr int NR = 32, D = kGluDepth;
     const int lane = threadIdx.x & 63, S = (int)(blockDim.x >> 6);
     const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    // the workgroup's tile: column half `half` of granule ct (tsg_i8gemv.hip's numbering)
-    const int idx = (int)blockIdx.x >> 3;
-    const int ct = (idx >> 1) * 8 + ((int)blockIdx.x & 7), half = idx & 1;
-    const int n0 = kI8WaveN * ct + 32 * half;
+    // the workgroup's tile: column half `half` of granule ct
+    const I8SplitKTile t = i8_splitk_tile((int)blockIdx.x);
+    const int ct = t.ct, half = t.half, n0 = kI8WaveN * ct + 32 * half;
     if (n0 >= N) return;  // (uniform) a workgroup of the grid's padding to 16
 
     const size_t boff = ((size_t)ct * nks * 64 + lane) * 4 + 2 * half;  // step ks at + 256 ks
     const uint32_t *bg = img_g + boff, *bu = img_u + boff;
     const int row = lane & 31, kl = 16 * (lane >> 5);
-    const int8_t *xr = X + (size_t)(row < M ? row : 0) * K;
-    const int cnt = nks > w ? (nks - w + S - 1) / S : 0;  // the wave's steps
+    const int8_t *xr = i8_arow(X, row, M, K);
+    const int cnt = i8_wave_steps(nks, w, S);
 
     uint32_t bq[D][2][2];  // [slot][matrix][k half]
     v4i a[D][2];
@@ -247,24 +224,9 @@ __global__ __launch_bounds__(64 * kI8GluWaves) void tsg_i8glu_gemv_kernel(const 
             const uint2 vg = *reinterpret_cast<const uint2 *>(bg + (size_t)ks * 256);
             const uint2 vu = *reinterpret_cast<const uint2 *>(bu + (size_t)ks * 256);
             bq[d][0][0] = vg.x, bq[d][0][1] = vg.y, bq[d][1][0] = vu.x, bq[d][1][1] = vu.y;
-#pragma unroll
-            for (int kk = 0; kk < 2; kk++) {
-                const int k = ks * kI8KStep + 32 * kk + kl;
-                if (xvec) {  // K % 16 == 0: a piece is inside a row or past its end
-                    const bool in = row < M && k < K;
-                    const v4i v = *reinterpret_cast<const v4i *>(xr + (in ? k : 0));
-                    a[d][kk] = in ? v : v4i{0, 0, 0, 0};
-                } else {
-                    uint32_t x[4] = {0, 0, 0, 0};
-                    if (row < M)
-                        for (int e = 0; e < 16 && k + e < K; e++)
-                            x[e >> 2] |= (uint32_t)(uint8_t)xr[k + e] << (8 * (e & 3));
-                    a[d][kk] = v4i{(int)x[0], (int)x[1], (int)x[2], (int)x[3]};
-                }
-            }
+            i8_afrag_pair(xr, row < M, kl, ks, K, xvec, a[d]);
         } else {
-#pragma unroll
-            for (int kk = 0; kk < 2; kk++) a[d][kk] = v4i{0, 0, 0, 0};
+            i8_afrag_zero(a[d]);
         }
     };
 
@@ -294,24 +256,24 @@ __global__ __launch_bounds__(64 * kI8GluWaves) void tsg_i8glu_gemv_kernel(const 
         }
     }
 
-    // register j = 16 matrix + r of the wave -> red[(w NR + j) 64 + lane]; its first row is 8 (r / 4) + r % 4
+    // register j = 16 matrix + r of the wave -> red[(w NR + j) 64 + lane]
 #pragma unroll
     for (int mx = 0; mx < 2; mx++)
 #pragma unroll
         for (int r = 0; r < 16; r++)
-            if (8 * (r >> 2) + (r & 3) < M) red[(w * NR + 16 * mx + r) * 64 + lane] = acc[mx][0][r] + acc[mx][1][r];
+            if (mfma_row0(r) < M) red[(w * NR + 16 * mx + r) * 64 + lane] = acc[mx][0][r] + acc[mx][1][r];
     __syncthreads();
 
     const int n = n0 + (lane & 31);
     const GluCol c = glu_col<PRELU>(o, n < N ? n : n0);
     for (int r = w; r < 16; r += S) {
-        if (8 * (r >> 2) + (r & 3) >= M) continue;  // (uniform) a register of padding rows
+        if (mfma_row0(r) >= M) continue;  // (uniform) a register of padding rows
         int sg = 0, su = 0;
         for (int s = 0; s < S; s++) {
             sg += red[(s * NR + r) * 64 + lane];
             su += red[(s * NR + 16 + r) * 64 + lane];
         }
-        const int m = 8 * (r >> 2) + 4 * (lane >> 5) + (r & 3);
+        const int m = mfma_row(r, lane);
         if (m < M && n < N) glu_store1<PRELU>(Y, o, c, sg, su, m, n);
     }
 }
@@ -321,7 +283,7 @@ __global__ __launch_bounds__(64 * kI8GluWaves) void tsg_i8glu_gemv_kernel(const 
 // !tile: the split-K variant.
 int launch_tcsc_i8glu(const int8_t *X, const uint32_t *img, int K, const YOut &o, bool tile)
 {
-    if (o.M < 1 || !o.img_up || !o.b_up) return -2;  // (run_glu sends no other call here)
+    if (o.M < 1 || !o.img_up || !o.b_up) return -2;  // (run_mfma sends no other call here)
     GluOut g;
     g.b = o.b, g.alpha = o.alpha, g.cs = o.cs, g.b_up = o.b_up, g.cs_up = o.cs_up, g.rs = o.rs;
     g.ep = o.ep;
@@ -329,8 +291,7 @@ int launch_tcsc_i8glu(const int8_t *X, const uint32_t *img, int K, const YOut &o
     g.ep.bits &= ~kEpiActMask;  // applied before the multiply by u, not by epi_store1
     g.ytype = o.ytype | (g.ep.on() ? kYEpi : 0);
     g.ldY = o.ldY;
-    const int nks = (K + kI8KStep - 1) / kI8KStep;
-    const int xvec = K > 0 && K % 16 == 0 && ((uintptr_t)X & 15) == 0;
+    const int nks = i8_nks(K), xvec = x_vec_ok(X, K, 16);
     const int64_t granules = ((int64_t)o.N + kI8WaveN - 1) / kI8WaveN;
     float *Y = static_cast<float *>(o.Y);
     if (!tile && o.M <= kI8GemvMaxM) {
@@ -342,8 +303,9 @@ int launch_tcsc_i8glu(const int8_t *X, const uint32_t *img, int K, const YOut &o
                            xvec);
     } else {
         const int64_t mtiles = ((int64_t)o.M + kI8TileM - 1) / kI8TileM;
-        if (granules * mtiles >= (1ll << 32) / kGluThreads) return -2;  // (run_glu refuses it first)
-        const dim3 grid((unsigned)(granules * mtiles)), block(kGluThreads);
+        // (run_mfma refuses it first; two workgroups per 128 x 128 tile: the grid stays under 2^32 threads)
+        if (!mfma_grid_ok(o.M, o.N, kI8TileM, kI8TileN, kI8Threads)) return -2;
+        const dim3 grid((unsigned)(granules * mtiles)), block(kI8Threads);
         auto *kernel = o.prelu ? tsg_i8glu_kernel<true> : tsg_i8glu_kernel<false>;
         hipLaunchKernelGGL(kernel, grid, block, 0, (hipStream_t)o.stream, X, img, o.img_up, g, Y, o.M, o.N, K, nks,
                            (int)granules, xvec);

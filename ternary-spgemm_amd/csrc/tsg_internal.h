@@ -418,6 +418,18 @@ constexpr int kI8WaveN = 64;                    // columns of a wave tile (image
 constexpr int kI8KStep = 64;
 constexpr int kI8MaxK = 131072;                 // 128 * K <= 2^24 (tsg_plan.h)
 constexpr uint32_t kI8Pos = 0, kI8Neg = 2, kI8Zero = 3;
+constexpr int kI8Threads = 256;                 // a workgroup of the tile kernels (tsg_i8mfma, tsg_i8glu)
+// The launch arithmetic every matrix-core launcher (and run_mfma, tsg_capi.cpp)
+// shares.  i8_nks: the k-steps of the image.  x_vec_ok: X may be read 16 bytes
+// at a time, `elems` elements -- every row then starts 16-byte aligned and a
+// piece is inside a row or past its end.  mfma_grid_ok: one workgroup of
+// `threads` per tile_m x tile_n tile of Y keeps the grid under 2^31 threads.
+inline int i8_nks(int K) { return (K + kI8KStep - 1) / kI8KStep; }
+inline int x_vec_ok(const void *X, int K, int elems) { return K > 0 && K % elems == 0 && ((uintptr_t)X & 15) == 0; }
+inline bool mfma_grid_ok(int64_t M, int64_t N, int tile_m, int tile_n, int threads)
+{
+    return (M + tile_m - 1) / tile_m * ((N + tile_n - 1) / tile_n) < (1ll << 31) / threads;
+}
 struct I8Geom {
     int Kp = 0, Np = 0;                         // K, N padded to kI8KStep, kI8TileN
     int64_t words() const { return (int64_t)Kp * Np / 16; }
@@ -463,7 +475,7 @@ inline I8GemvPick i8gemv_pick(int K, int N)
 {
     I8GemvPick p;
     p.tn = N / kI8WaveN >= kI8GemvCUs ? 64 : 32;
-    const int nks = (K + kI8KStep - 1) / kI8KStep, cap = p.tn == 64 ? kI8GemvWaves64 : kI8GemvWaves32;
+    const int nks = i8_nks(K), cap = p.tn == 64 ? kI8GemvWaves64 : kI8GemvWaves32;
     for (p.S = 1; 2 * p.S <= cap && 2 * p.S <= nks;) p.S *= 2;
     return p;
 }
@@ -480,7 +492,7 @@ int launch_tcsc_i8gemv(const int8_t *X, const uint32_t *img, int K, const YOut &
 constexpr int kI8GluWaves = kI8GemvLds / (32 * 256);
 inline int i8glu_pick(int K)
 {
-    const int nks = (K + kI8KStep - 1) / kI8KStep;
+    const int nks = i8_nks(K);
     int S = 1;
     while (2 * S <= kI8GluWaves && 2 * S <= nks) S *= 2;
     return S;

@@ -11,9 +11,9 @@
 // is exact in fp32 (the contract and its error bound: include/ternary_spgemm.h).
 // A dense pass multiplies by W's zeros too: an inf or NaN in a row of X makes
 // that row of Y unspecified (inf * 0) and no other.  Everything after the chain
-// is the walks' epilogue through the shared helpers: scale_bias (tsg_scale.h),
-// the PReLU rule, epi_store1 (tsg_epilogue.h) and the one rounding of
-// tsg_ytype.h, one element per lane.
+// is the walks' epilogue, finish_store1 (tsg_epilogue.h): scale_bias, the PReLU
+// rule, the fused epilogue and the one rounding of tsg_ytype.h, one element per
+// lane by the register map of tsg_i8frag.h (mfma_row).
 //
 // Split.  Workgroup: 256 threads = 4 waves side by side, tile 128 rows x 256
 // columns; a wave owns 128 x 64 -- one 64-column granule of the image -- as
@@ -58,8 +58,8 @@
 #include <cstdint>
 
 #include "tsg_epilogue.h"
+#include "tsg_i8frag.h"
 #include "tsg_internal.h"
-#include "tsg_scale.h"
 #include "tsg_ytype.h"
 
 namespace tsg {
@@ -214,10 +214,6 @@ __global__ __launch_bounds__(kX16Threads, 2) void tsg_x16mfma_kernel(
     }
     if (!live) return;
 
-    // Accumulator register r of a 32 x 32 tile: lanes 0-31 hold the 32 columns
-    // of row 8 (r / 4) + r % 4, lanes 32-63 those of the row 4 below -- one
-    // coalesced row segment per register and half wave, one element per lane
-    // (the map at the end of tsg_i8mfma.hip)
     const int yt = ytype & kYTypeMask;
     const bool has_rs = rs != nullptr, has_cs = cs != nullptr, epi = (ytype & kYEpi) != 0;
     // rows outermost, so that a row's scale is loaded once and used at once
@@ -234,20 +230,14 @@ __global__ __launch_bounds__(kX16Threads, 2) void tsg_x16mfma_kernel(
     for (int rt = 0; rt < RT; rt++)
 #pragma unroll
         for (int r = 0; r < 16; r++) {
-            const int m = m0 + 32 * rt + 8 * (r >> 2) + 4 * (lane >> 5) + (r & 3);
+            const int m = m0 + 32 * rt + mfma_row(r, lane);
             if (m >= M) continue;
             const float rm = has_rs ? rs[m] : 0.0f;
 #pragma unroll
-            for (int c2 = 0; c2 < 2; c2++) {
-                const int n = nn[c2];
-                if (n >= N) continue;
-                float v = scale_bias(acc[rt][c2][r], has_rs, rm, has_cs, cn[c2], bn[c2]);
-                if (PRELU) v = (v > 0) ? v : an[c2] * v;  // comp_prelu.h:57-67
-                if (epi)  // a fused epilogue (uniform: the launcher's flag; tsg_epilogue.h)
-                    epi_store1(Y, yt, ldY, ep, m, n, v);
-                else
-                    ystore1_any(Y, yt, (size_t)m * (size_t)ldY + n, v);
-            }
+            for (int c2 = 0; c2 < 2; c2++)
+                if (nn[c2] < N)
+                    finish_store1<PRELU>(Y, yt, epi, ldY, ep, m, nn[c2], acc[rt][c2][r], has_rs, rm, has_cs, cn[c2], bn[c2],
+                                         an[c2]);
         }
 }
 
@@ -270,16 +260,14 @@ auto x16_kernel(bool bf16, bool low, bool prelu)
 
 int launch_tcsc_x16mfma(const void *X, int xtype, const uint32_t *img, int K, const YOut &o)
 {
-    const int64_t ntiles = (o.N + kX16TileN - 1) / kX16TileN, mtiles = (o.M + kX16TileM - 1) / kX16TileM;
-    if (ntiles * mtiles >= (1ll << 31) / kX16Threads) return -2;  // (run_x16 refuses it first)
+    if (!mfma_grid_ok(o.M, o.N, kX16TileM, kX16TileN, kX16Threads)) return -2;  // (run_mfma refuses it first)
     if (xtype != kXF16 && xtype != kXBF16) return -2;
-    const int nks = (K + kI8KStep - 1) / kI8KStep;
-    const int xvec = K > 0 && K % 8 == 0 && ((uintptr_t)X & 15) == 0;
+    const int64_t ntiles = (o.N + kX16TileN - 1) / kX16TileN, mtiles = (o.M + kX16TileM - 1) / kX16TileM;
     const dim3 grid((unsigned)(ntiles * mtiles)), block(kX16Threads);
     auto *kernel = x16_kernel(xtype == kXBF16, o.M <= 64, o.prelu);
     hipLaunchKernelGGL(kernel, grid, block, 0, (hipStream_t)o.stream, static_cast<const uint16_t *>(X),
                        reinterpret_cast<const uint4 *>(img), o.b, o.alpha, o.rs, o.cs, o.ep, static_cast<float *>(o.Y), o.ldY,
-                       o.kernel_ytype(false), o.M, o.N, K, nks, (int)ntiles, xvec);
+                       o.kernel_ytype(false), o.M, o.N, K, i8_nks(K), (int)ntiles, x_vec_ok(X, K, 8));
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
